@@ -1,18 +1,24 @@
 #!/usr/bin/env python
 """Benchmark of the hot path: colourised 216x384 frames/s/GPU (BASELINE.json `metric`).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
-A "step" = one frame of the clip recurrence of /root/reference/test.py:68-96 (frame t consumes frame t-1's
+A "step" = one frame of the clip recurrence of test.py:68-96 (frame t consumes frame t-1's
 prediction): VGG19(A) -> WarpNet(A) + fused correlation -> ColorVidNet on one synthetic 1x3x216x384 Lab frame
 already resident in HBM.  The K timed steps go through `ClipColorizer.clip` (front end of the next frames on side
-HIP streams, ColorVidNet recurrence on the main one; bit-identical to per-frame `frame_colorization` calls, which
-are timed right after and reported as `config.per_frame_api_frames_per_s`; `--lookahead 0` times those instead).
-The K-step clip is timed `config.repeats` times back to back (same frames, same recurrence start, each repeat bracketed by
-barrier + synchronize; enough repeats for >= 0.5 s of timed GPU work whatever K is): `ms_per_step` / `value` are the MEDIAN
-repeat, p10 / p90 are in `config` (">= 50 timed, median + p10/p90").
+HIP streams, ColorVidNet recurrence on the main one; bit-identical to per-frame `frame_colorization` calls;
+`--lookahead 0` times those instead).  After the W warm-up steps the K-step clip is timed ONCE (bracketed by
+barrier + synchronize): `ms_per_step` = that pass / K, `value` = frames/s/GPU of it.
+`--dump-outputs DIR` writes what the timed path returned for its last step (`ab.npy`: the ab prediction [1,2,H,W];
+`last_lab.npy`: test.py:96's [L, ab] [1,3,H,W]; float32) once the timed pass is over; the frames and weights are
+seeded, so the same arguments give the same inputs in every run.
+A plain run does only that.  `--full` adds everything else, after the timed pass: the K-step clip repeated
+`config.repeats` times (enough for >= 0.5 s of timed GPU work; median, p10 / p90 in `config`: SURVEY.md §8(d)),
+the per-frame API, the reference's unmodified loop, eager launches, the multi-reference and batched-clips legs,
+the correlation roofline, the Winograd-everywhere engine, the other BASELINE configurations, the CPU baseline and
+the parity block.
 N=1 runs BASELINE.json configs[1].  With N>1 each rank colourises its own contiguous chunk of K frames (weak
 scaling; the exemplar-side tensors are computed on rank 0 and broadcast once over RCCL/xGMI; no collective in
 the per-frame path).  `--gpus N` with N > 1 outside torch.distributed.run re-launches itself under it (one process
@@ -403,6 +409,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=60)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned for its last step as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed pass, also run the repeats (p10 / p90), the side legs, the roofline, the CPU baseline "
+                         "and the parity block; the options below apply to these")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-speed-leg", action="store_true", help="skip the config.engine_speed leg (the K frames under DVC_CONV_ALGO=speed)")
     ap.add_argument("--no-parity", action="store_true", help="skip the untimed parity block (GPU and CPU fp32 against the fp64 oracle)")
@@ -574,22 +585,69 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # one untimed pass of the K steps: sizes the number of repeats (the same on every rank) and is the last piece of warm-up
+    # the timed region: the K steps, once
     bracket()
     t0 = time.perf_counter()
-    timed_clip()
+    last_timed = timed_clip()
     bracket()
-    est = torch.tensor([time.perf_counter() - t0], device=device, dtype=torch.float64)
+    t_pass = torch.tensor([time.perf_counter() - t0], device=device, dtype=torch.float64)
     if use_dist:
-        dist.all_reduce(est, op=dist.ReduceOp.MAX)
-    repeats = int(min(400, max(3, -(-args.min_timed_s // max(est.item(), 1e-6)))))
+        dist.all_reduce(t_pass, op=dist.ReduceOp.MAX)   # the slowest rank
+    elapsed = t_pass.item()
+    assert torch.isfinite(last_timed).all(), "non-finite output"
+    fps = n_gpus * K / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"ab": last_timed[:, 1:3], "last_lab": last_timed})
+
+    run = argparse.Namespace(K=K, Wm=Wm, cc=cc, nets=nets, sd=sd, frames=frames, device=device, rank=rank, n_gpus=n_gpus,
+                             use_dist=use_dist, use_graph=use_graph, clip_graph=clip_graph, IB=IB, graph_note=graph_note,
+                             step=step, timed_clip=timed_clip, bracket=bracket, last=last, last_timed=last_timed, fps=fps,
+                             elapsed=elapsed)
+    legs = full_legs(args, run) if args.full else {}
+    if rank == 0:
+        print(json.dumps(result_line(args, run, legs)), flush=True)
+    if use_dist:
+        dist.destroy_process_group()
+
+
+def dump_outputs(out_dir, arrays, budget_bytes=64 << 20):
+    """DIR/<name>.npy for each array, float32 (float64 stays float64); an array beyond what is left of the 64 MB budget
+    is replaced by a fixed, seeded sample of its flattened values (sorted indices, same sample in every run)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        if a.dtype != np.float64:
+            a = a.astype(np.float32)
+        if a.nbytes > budget_bytes:
+            n = budget_bytes // a.itemsize
+            a = a.ravel()[np.sort(np.random.default_rng(0).choice(a.size, n, replace=False))]
+            log(f"[bench] --dump-outputs: {name} sampled to {n} values")
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        budget_bytes -= a.nbytes
+    log(f"[bench] outputs of the last timed step written to {out_dir}: {', '.join(arrays)}")
+
+
+def full_legs(args, run):
+    """--full: everything the benchmark measures and checks beyond the headline, after the timed pass (`run`: main()'s
+    state at that point).  Returns the blocks of the result line it fills."""
+    (K, Wm, cc, nets, sd, frames, device, rank, n_gpus, use_dist, use_graph, clip_graph, IB, step, timed_clip, bracket, last,
+     last_timed, fps) = (run.K, run.Wm, run.cc, run.nets, run.sd, run.frames, run.device, run.rank, run.n_gpus, run.use_dist,
+                         run.use_graph, run.clip_graph, run.IB, run.step, run.timed_clip, run.bracket, run.last,
+                         run.last_timed, run.fps)
+    from dvc_amd import ops, synth
+    from dvc_amd.frame import ClipColorizer
+    # the K-step clip repeated back to back (same frames, same recurrence start, each repeat bracketed by barrier +
+    # synchronize; enough repeats for >= --min-timed-s of timed GPU work, the same number on every rank): median, p10 / p90
+    repeats = int(min(400, max(3, -(-args.min_timed_s // max(run.elapsed, 1e-6)))))
     rep_s = []
     for _ in range(repeats):
         bracket()
         t0 = time.perf_counter()
-        last_timed = timed_clip()
+        timed_clip()
         bracket()
         rep_s.append(time.perf_counter() - t0)
+
     def median_s(fn, n):
         """Median wall time of `fn()` over n runs (each synchronised), and its last result."""
         ts, res = [], None
@@ -702,15 +760,11 @@ def main():
                            "batch-aware launch plan; per-clip results equal the single-clip driver's to fp32 rounding of the summation "
                            "order (tests/test_gpu_refs.py)"}
     last_before = last          # recurrence state the timed clip started from
-    last = last_timed
     t = torch.tensor(rep_s, device=device, dtype=torch.float64)
     if use_dist:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)        # per repeat: the slowest rank
     rep_sorted = sorted(t.tolist())
     pick = lambda q: rep_sorted[min(len(rep_sorted) - 1, max(0, int(round(q * (len(rep_sorted) - 1)))))]   # noqa: E731
-    elapsed = pick(0.5)                                 # the MEDIAN repeat of exactly K steps
-    assert torch.isfinite(last).all(), "non-finite output"
-    fps = n_gpus * K / elapsed
 
     # ---- roofline of the north-star kernel: HIP events on the launch stream, on the CLIP'S OWN operands — theta of
     # the first timed frame (VGG19 -> WarpNet heads/trunk -> 1x1 -> centre/normalise, exactly what frame_colorization
@@ -872,65 +926,80 @@ def main():
                          f"{time.perf_counter() - t_o:.1f} s of this run; corr_launch_us / corr_frac: the configuration's correlation "
                          "launch set on the clip's own operands, HIP events")
 
-    if rank == 0:
-        line = {
-            "metric": f"colorized frames/sec/GPU at {H}x{W}; correlation HBM GB/s vs roofline",
-            "value": round(fps, 3), "unit": "frames/s", "n_gpus": n_gpus, "steps": K, "warmup": Wm,
-            "ms_per_step": round(elapsed / K * 1e3, 4), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": ("BASELINE configs[1]: 1x3x216x384" if (H, W) == (216, 384) else f"1x3x{H}x{W}") +
-                                   " frame + one exemplar per step, HIP "
-                                   "VGG19 + WarpNet/fused correlation + ColorVidNet forward, fp32, clip "
-                                   "recurrence as test.py:68-96",
-                       "H": H, "W": W, "temperature": 1e-10, "weights": "synthetic seed 0",
-                       "correlation": "fp32 MFMA" if args.corr == "fp32" else
-                       "bf16 MFMA candidate filter + exact fp32 re-scoring (configs[4])",
-                       "exemplar_side": "recomputed per frame" if args.no_exemplar_cache else "cached per clip",
-                       "conv_algorithm": {"auto": "Winograd F(2x2,3x3) on the fp32 matrix cores where ops.winograd_selected "
-                                                  "picks it (3x3 stride-1 layers with >= 13x24 outputs, minus the layers of the "
-                                                  "error-aware engine map arch.DIRECT_LAYERS: %s), direct implicit GEMM elsewhere; "
-                                                  "fp32 throughout" % (",".join(sorted(ops.direct_layers())) or "none"),
-                                          "speed": "Winograd F(2x2,3x3) on every 3x3 stride-1 layer with >= 13x24 outputs (geometry "
-                                                   "rule only, no error-aware map)",
-                                          "winograd": "Winograd F(2x2,3x3) on every eligible 3x3 layer",
-                                          "direct": "direct implicit GEMM everywhere"}[ops.conv_algo()],
-                       "conv_tile_choice": "autotuned on first use during warm-up (cf. cudnn.benchmark=True, test.py:140)"
-                       if ops.autotune_enabled() else "the library's static plan (deterministic: the arithmetic the parity tests assert)",
-                       "frames_per_gpu": K, "parallelism": f"frame-chunks x{n_gpus}",
-                       "repeats": repeats, "ms_per_step_p10": round(pick(0.1) / K * 1e3, 4),
-                       "ms_per_step_p90": round(pick(0.9) / K * 1e3, 4),
-                       "timed_gpu_seconds": round(sum(rep_sorted), 3),
-                       "timing": f"the K = {K} step clip timed {repeats} times back to back from the same recurrence state, every "
-                                 "repeat bracketed by barrier + synchronize; ms_per_step / value = the median repeat",
-                       "clip_driver": "per-frame calls, one stream" if args.lookahead <= 0 else
-                       f"ClipColorizer.clip: front end of the next {args.lookahead} frames on side HIP streams, " +
-                       (f"{args.front_batch} frames per set of front-end launches (planned per image), " if args.front_batch > 1 else "") +
-                       "ColorVidNet recurrence on the main stream (bit-identical to per-frame calls)",
-                       "launches": ("look-ahead front ends replayed as hipGraphs (one captured sequence per side stream), ColorVidNet "
-                                    "chain launched kernel by kernel; per-frame API: both sequences replayed; bit-identical to "
-                                    "eager launches (fixed mode, no warm-up trial)") if use_graph else
-                                   (graph_note or "every kernel launched from Python"),
-                       "engine_speed": speed_leg,
-                       "per_frame_api_frames_per_s": None if seq_fps is None else round(seq_fps, 3),
-                       "dropin_unmodified_frames_per_s": None if dropin is None else dropin["frames_per_s"],
-                       "dropin_unmodified": None if dropin is None else dict(
-                           dropin, note="the reference's own loop, test.py:57-96, verbatim: features_B computed by the caller, "
-                                        "frame_colorization(...) called positionally per frame with the same exemplar tensors, no "
-                                        "ClipColorizer in the caller, every launch from Python; the exemplar side is memoised behind "
-                                        "the call on the identity / version counters of the caller's tensors (bit-identical to "
-                                        "recomputing it; tests/test_gpu_dropin_loop.py)"),
-                       "eager_launch_clip_driver_frames_per_s": None if eager_fps is None else round(eager_fps, 3),
-                       "batched_clips": batched,
-                       "other_configs": other,
-                       "multi_reference": None if multi is None else dict(
-                           multi, speedup_vs_one_pass_per_reference=round(multi["frame_colorizations_per_s"] / (fps / n_gpus), 3))},
-            "roofline": roof,
-            "cpu_baseline": cpu,
-            "parity": parity,
-        }
-        print(json.dumps(line), flush=True)
-    if use_dist:
-        dist.destroy_process_group()
+    return {"repeats": {"repeats": repeats, "ms_per_step_median": round(pick(0.5) / K * 1e3, 4),
+                        "ms_per_step_p10": round(pick(0.1) / K * 1e3, 4), "ms_per_step_p90": round(pick(0.9) / K * 1e3, 4),
+                        "timed_gpu_seconds": round(sum(rep_sorted), 3),
+                        "note": f"the K = {K} step clip timed {repeats} more times back to back after the timed pass, from the same "
+                                "recurrence state, every repeat bracketed by barrier + synchronize"},
+            "speed_leg": speed_leg, "seq_fps": seq_fps, "dropin": dropin, "eager_fps": eager_fps, "batched": batched,
+            "other": other, "multi": multi, "roof": roof, "cpu": cpu, "parity": parity}
+
+
+def result_line(args, run, legs):
+    """The ONE JSON line; `legs` holds full_legs()'s blocks (empty in a plain run: those blocks are null)."""
+    from dvc_amd import ops
+    K, Wm, n_gpus, fps, elapsed = run.K, run.Wm, run.n_gpus, run.fps, run.elapsed
+    rep = legs.get("repeats")
+    speed_leg, seq_fps, dropin, eager_fps = legs.get("speed_leg"), legs.get("seq_fps"), legs.get("dropin"), legs.get("eager_fps")
+    multi = legs.get("multi")
+    return {
+        "metric": f"colorized frames/sec/GPU at {H}x{W}; correlation HBM GB/s vs roofline",
+        "value": round(fps, 3), "unit": "frames/s", "n_gpus": n_gpus, "steps": K, "warmup": Wm,
+        "ms_per_step": round(elapsed / K * 1e3, 4), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": ("BASELINE configs[1]: 1x3x216x384" if (H, W) == (216, 384) else f"1x3x{H}x{W}") +
+                               " frame + one exemplar per step, HIP "
+                               "VGG19 + WarpNet/fused correlation + ColorVidNet forward, fp32, clip "
+                               "recurrence as test.py:68-96",
+                   "H": H, "W": W, "temperature": 1e-10, "weights": "synthetic seed 0",
+                   "correlation": "fp32 MFMA" if args.corr == "fp32" else
+                   "bf16 MFMA candidate filter + exact fp32 re-scoring (configs[4])",
+                   "exemplar_side": "recomputed per frame" if args.no_exemplar_cache else "cached per clip",
+                   "conv_algorithm": {"auto": "Winograd F(2x2,3x3) on the fp32 matrix cores where ops.winograd_selected "
+                                              "picks it (3x3 stride-1 layers with >= 13x24 outputs, minus the layers of the "
+                                              "error-aware engine map arch.DIRECT_LAYERS: %s), direct implicit GEMM elsewhere; "
+                                              "fp32 throughout" % (",".join(sorted(ops.direct_layers())) or "none"),
+                                      "speed": "Winograd F(2x2,3x3) on every 3x3 stride-1 layer with >= 13x24 outputs (geometry "
+                                               "rule only, no error-aware map)",
+                                      "winograd": "Winograd F(2x2,3x3) on every eligible 3x3 layer",
+                                      "direct": "direct implicit GEMM everywhere"}[ops.conv_algo()],
+                   "conv_tile_choice": "autotuned on first use during warm-up (cf. cudnn.benchmark=True, test.py:140)"
+                   if ops.autotune_enabled() else "the library's static plan (deterministic: the arithmetic the parity tests assert)",
+                   "frames_per_gpu": K, "parallelism": f"frame-chunks x{n_gpus}",
+                   "timed_gpu_seconds": round(elapsed, 3),
+                   "timing": f"the K = {K} step clip timed once after the warm-up, bracketed by barrier + synchronize; "
+                             "ms_per_step / value = that pass",
+                   "repeats": None if rep is None else rep["repeats"],
+                   "ms_per_step_p10": None if rep is None else rep["ms_per_step_p10"],
+                   "ms_per_step_p90": None if rep is None else rep["ms_per_step_p90"],
+                   "repeated_clip": rep,
+                   "clip_driver": "per-frame calls, one stream" if args.lookahead <= 0 else
+                   f"ClipColorizer.clip: front end of the next {args.lookahead} frames on side HIP streams, " +
+                   (f"{args.front_batch} frames per set of front-end launches (planned per image), " if args.front_batch > 1 else "") +
+                   "ColorVidNet recurrence on the main stream (bit-identical to per-frame calls)",
+                   "launches": ("look-ahead front ends replayed as hipGraphs (one captured sequence per side stream), ColorVidNet "
+                                "chain launched kernel by kernel; per-frame API: both sequences replayed; bit-identical to "
+                                "eager launches (fixed mode, no warm-up trial)") if run.use_graph else
+                               (run.graph_note or "every kernel launched from Python"),
+                   "engine_speed": speed_leg,
+                   "per_frame_api_frames_per_s": None if seq_fps is None else round(seq_fps, 3),
+                   "dropin_unmodified_frames_per_s": None if dropin is None else dropin["frames_per_s"],
+                   "dropin_unmodified": None if dropin is None else dict(
+                       dropin, note="the reference's own loop, test.py:57-96, verbatim: features_B computed by the caller, "
+                                    "frame_colorization(...) called positionally per frame with the same exemplar tensors, no "
+                                    "ClipColorizer in the caller, every launch from Python; the exemplar side is memoised behind "
+                                    "the call on the identity / version counters of the caller's tensors (bit-identical to "
+                                    "recomputing it; tests/test_gpu_dropin_loop.py)"),
+                   "eager_launch_clip_driver_frames_per_s": None if eager_fps is None else round(eager_fps, 3),
+                   "batched_clips": legs.get("batched"),
+                   "other_configs": legs.get("other"),
+                   "multi_reference": None if multi is None else dict(
+                       multi, speedup_vs_one_pass_per_reference=round(multi["frame_colorizations_per_s"] / (fps / n_gpus), 3)),
+                   "full": bool(args.full)},
+        "roofline": legs.get("roof"),
+        "cpu_baseline": legs.get("cpu"),
+        "parity": legs.get("parity"),
+    }
 
 
 if __name__ == "__main__":

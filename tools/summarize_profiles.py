@@ -1,5 +1,6 @@
-"""Copy the judged profile summaries from gpurun_out/ (scratch) into profiles/ (tracked).
-    python tools/summarize_profiles.py r01
+"""Copy the judged profile summaries from $OUT (raw artefacts, default out/: where tools/gpu_check.sh and gpu_final.sh
+write) into profiles/ (tracked).
+    OUT=<dir> python tools/summarize_profiles.py r01
 Produces profiles/<round>_bench_kernel_stats.csv (rocprofv3 --kernel-trace --stats of `bench.py`),
 profiles/<round>_bench_line.json (the JSON line printed under the profiler) and
 profiles/<round>_pmc_summary.md (derived metrics from the separate --pmc passes)."""
@@ -12,7 +13,7 @@ import shutil
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-G = os.path.join(ROOT, "gpurun_out")
+G = os.path.join(ROOT, os.environ.get("OUT", "out"))
 P = os.path.join(ROOT, "profiles")
 tag = sys.argv[1] if len(sys.argv) > 1 else "r01"
 os.makedirs(P, exist_ok=True)
@@ -46,7 +47,7 @@ def load(path):
 
 
 def table(prefix, title, note):
-    """Markdown table of the derived per-kernel metrics of the passes gpurun_out/<prefix>1..4 (None if the passes are absent)."""
+    """Markdown table of the derived per-kernel metrics of the passes $OUT/<prefix>1..4 (None if the passes are absent)."""
     dur = collections.defaultdict(list)
     for r in load(os.path.join(G, prefix + "1", "p_kernel_trace.csv")):
         dur[r["Kernel_Name"]].append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
