@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # DVC_DEBUG_LIB=1 (tools/ only) loads the -DDVC_DEBUG build, the only one that carries the dvc_debug_* hooks
 DEBUG_BUILD = os.environ.get("DVC_DEBUG_LIB", "0") == "1"
 LIB_PATH = os.path.join(_HERE, "libdvc_hip_debug.so" if DEBUG_BUILD else "libdvc_hip.so")
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 c_float_p = ctypes.c_void_p
 c_i32 = ctypes.c_int32
@@ -118,6 +118,10 @@ SIGNATURES = {
                                          _VP, _VP, _VP, _VP, _VP, _VP, ctypes.c_size_t, _VP]),
     "dvc_corr_softmax_bwd": (ctypes.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, ctypes.c_float, ctypes.c_float, c_i32, c_i32, c_i32, c_i64, c_i32,
                                             _VP, _VP, _VP, _VP]),
+    "dvc_nlwa_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32, c_i32, c_i32, c_i32]),
+    "dvc_nlwa_fwd": (ctypes.c_int, [_VP, c_i32, c_i32, c_i32, _VP, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.c_float,
+                                    ctypes.c_float, ctypes.c_float, ctypes.c_float, c_i32, ctypes.c_float, _VP, _VP,
+                                    ctypes.c_size_t, _VP]),
 }
 # diagnostics for tools/ (include/dvc_hip.h, last section): exported by the -DDVC_DEBUG build only
 DEBUG_SIGNATURES = {

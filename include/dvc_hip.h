@@ -30,7 +30,7 @@ extern "C" {
 
 typedef void* dvcStream; /* hipStream_t */
 
-#define DVC_ABI_VERSION 19
+#define DVC_ABI_VERSION 20
 
 int dvc_abi_version(void);
 /* Thread-local description of the last failure (empty string if none). */
@@ -478,6 +478,22 @@ int dvc_corr_softmax_bwd(const float* f_blk, const float* blab, const float* gy,
                          const float* gsim, const int32_t* argmax, float temperature, float wta_scale, int32_t batch, int32_t rows, int32_t P,
                          int64_t chan_stride, int32_t ld_t, float* rowstat_scratch, float* dS, float* dST,
                          dvcStream stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Non-local weighted average (models/NonlocalNet.py:86-111, NonlocalWeightedAverage; find_local_patch :12-17), the
+ * training-side smoothness term: per image, with x_lab and feature nearest-resized to H x W (N = H W),
+ *     U = find_local_patch(feature, k)  [C k k][N];   A = softmax_j(U^T U / alpha);   out[2][N] = (A ab^T)^T
+ * as one fused pass (dvc_amd/nonlocal_avg.py): nothing N x N and nothing k*k-times unfolded is materialised.
+ * x_lab [B][Cx][Hx][Wx] (channels 1..2 are read), feature [B][C][Hf][Wf], out [B][2][H][W], all fp32 contiguous.
+ * scale_x* / scale_f*: the source-index scales of the two nearest resizes, src = min(floor(dst * scale), in - 1) — the
+ * float ATen derives (1 / scale_factor when a factor is given, in / out when a size is).  patch_size odd >= 1, alpha > 0.
+ * workspace: dvc_nlwa_workspace_bytes(B, C, patch_size, H, W) bytes, 256-byte aligned; it holds, at 256-byte aligned offsets,
+ * the zero-bordered resized feature F_pad [B][Cp][H + 2 (k/2)][W + 2 (k/2)] (Cp = C rounded up to 32, zero planes), then the
+ * resized ab [B][2][N], then the partial softmax states.  Deterministic; an image's result does not depend on B. */
+size_t dvc_nlwa_workspace_bytes(int32_t B, int32_t C, int32_t patch_size, int32_t H, int32_t W);
+int dvc_nlwa_fwd(const float* x_lab, int32_t Cx, int32_t Hx, int32_t Wx, const float* feature, int32_t C, int32_t Hf, int32_t Wf,
+                 int32_t B, int32_t H, int32_t W, float scale_xh, float scale_xw, float scale_fh, float scale_fw, int32_t patch_size,
+                 float alpha, float* out, void* workspace, size_t workspace_bytes, dvcStream stream);
 
 #ifdef DVC_DEBUG
 /* ------------------------------------------------------------------------------------------------
