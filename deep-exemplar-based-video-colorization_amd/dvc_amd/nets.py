@@ -9,8 +9,10 @@ so `load_state_dict(torch.load(...))`, `.parameters()`, `.eval()`, `.cuda()` beh
 only* (they give the parameters their reference names); no torch.nn forward is ever called — every
 forward pass is a sequence of libdvc_hip.so kernel launches on the current stream.
 
-Inference only: outputs never carry autograd history (the reference's training path,
-train.py:402-427, is out of scope — SURVEY.md §2 rows 12-13).
+Inference only, with one exception: VGG19_pytorch gives the input gradient (frozen weights) that the reference's training
+losses need (train.py:649-668 take the perceptual and contextual losses on the features of the predicted frame); WarpNet and
+ColorVidNet outputs never carry autograd history (the rest of the training path, train.py:402-427, is out of scope —
+SURVEY.md §2 rows 12-13).
 """
 import torch
 import torch.nn as nn
@@ -134,7 +136,43 @@ def _check_input(x, name):
         raise NotImplementedError(
             f"{name}: an input requires grad and autograd is enabled, but the HIP forward is inference-only "
             "(no backward kernels). Call it under torch.no_grad() as test.py:83 does, or detach the input; "
-            "gradients exist only for the fused correlation, see dvc_amd.corr_autograd.")
+            "gradients exist for VGG19_pytorch.forward (input gradient, frozen weights), tensor_lab2rgb, the fused "
+            "correlation (dvc_amd.corr_autograd) and the contextual losses.")
+
+
+def vgg_bwd_weight(w):
+    """The filters of a 3x3 stride-1 pad-1 convolution's input gradient: dL/dx = conv3x3(dL/dy, W^T flipped), [Cin][Cout][3][3]
+    — Cin and Cout swap places at the same H x W, so the forward's engines (ops.conv3x3) run it as they are."""
+    return w.detach().transpose(0, 1).flip(2, 3).contiguous()
+
+
+def vgg_bwd_weight_conv1(w, preprocess=True):
+    """conv1_1's [3][Cout][3][3] input-gradient filters (ops.vgg_conv1_bwd).  preprocess=True folds vgg_preprocess
+    (utils/util.py:347-352: x_bgr[c] = (x_rgb[2 - c] - mean[c]) * 255) in, so the result is d/d rgb: the output channels in
+    reverse order, times 255."""
+    wt = vgg_bwd_weight(w)
+    return (wt.flip(0) * 255.0).contiguous() if preprocess else wt
+
+
+class _VGGInputGrad(torch.autograd.Function):
+    """VGG19_pytorch.forward with the post-ReLU output of every convolution up to the deepest requested key saved; backward walks
+    the layers in reverse and returns d x only (the weights are frozen)."""
+
+    @staticmethod
+    def forward(ctx, x, module, out_keys, preprocess):
+        saved = {}
+        outs = module._forward(x, out_keys, preprocess, False, saved=saved)
+        ctx.module, ctx.out_keys, ctx.preprocess = module, tuple(out_keys), preprocess
+        ctx.saved_keys = tuple(saved)
+        ctx.save_for_backward(*saved.values())
+        ctx.set_materialize_grads(False)
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        saved = dict(zip(ctx.saved_keys, ctx.saved_tensors))
+        g_ext = {k: g.contiguous() for k, g in zip(ctx.out_keys, grads) if g is not None}
+        return ctx.module._input_grad(saved, g_ext, ctx.preprocess), None, None, None
 
 
 # ================================================================================================ VGG19
@@ -179,7 +217,70 @@ class VGG19_pytorch(nn.Module):
         return self.forward(IA_l, out_keys, preprocess=True, _gray=True)
 
     def forward(self, x, out_keys, preprocess=True, _gray=False):
+        if not _gray and x.is_cuda and x.requires_grad and torch.is_grad_enabled():
+            return self._forward_with_grad(x, out_keys, preprocess)
         _check_input(x, "VGG19_pytorch")
+        return self._forward(x, out_keys, preprocess, _gray)
+
+    def _forward_with_grad(self, x, out_keys, preprocess):
+        """The training path (train.py:649-668): outputs bit-identical to the no-grad forward, with a backward to x."""
+        if any(p.requires_grad for p in self.parameters()):
+            raise NotImplementedError(
+                "VGG19_pytorch: only the input gradient is built (no weight gradients); freeze the parameters as train.py "
+                "does (`for p in vggnet.parameters(): p.requires_grad = False`)")
+        for k in out_keys:
+            if k not in arch.VGG_KEYS:
+                raise KeyError(k)
+        if not out_keys:
+            return []
+        uniq = list(dict.fromkeys(out_keys))    # (a key requested twice: the same tensor twice, autograd adds its gradients)
+        outs = _VGGInputGrad.apply(x, self, uniq, preprocess)
+        return [outs[uniq.index(k)] for k in out_keys]
+
+    def _bwd_packs(self, name):
+        """kind -> packed input-gradient filters of a 3x3 layer (vgg_bwd_weight), in the module's cache under their own keys."""
+        w = getattr(self, name).weight
+        key = "vgg_bwd." + name
+
+        def get(kind):
+            if kind == "winograd":
+                return self._cache.get(key + ":wino", w, lambda w: ops.pack_winograd_weight(vgg_bwd_weight(w)))
+            if kind == "ws":
+                return self._cache.get(key + ":ws", w, lambda w: ops.pack_ws_weight(vgg_bwd_weight(w)))
+            return self._cache.get(key, w, lambda w: ops.pack_conv_weight(vgg_bwd_weight(w)))
+        return get
+
+    def _input_grad(self, saved, g_ext, preprocess):
+        """d x from the saved post-ReLU outputs R and the incoming gradients of the requested keys.  Layer by layer, deepest
+        first: dZ = (dX + g(r)) * [R > 0] (ops.vgg_act_bwd), or through a pool (ops.vgg_pool_act_bwd), then the convolution's
+        input gradient dX = conv3x3(dZ, W^T flipped) on the forward's engines; conv1_1's 3-channel one on ops.vgg_conv1_bwd."""
+        keys = arch.VGG_KEYS
+        conv_names = {("r%s" % n[4:].replace("_", "")): n for n, _, _ in arch.VGG_CONVS}
+        i = max((keys.index(k) for k in g_ext), default=-1)
+        g = None                    # gradient w.r.t. the output of keys[i] from the layers behind it
+        while i >= 0:
+            key = keys[i]
+            if key[0] == "p":
+                rk = keys[i - 1]
+                dZ = ops.vgg_pool_act_bwd(g, g_ext.get(key), g_ext.get(rk), saved[rk], avg=self._pool == "avg")
+                i, key = i - 1, rk
+            else:
+                dZ = ops.vgg_act_bwd(g, g_ext.get(key), saved[key], out=g)
+            name = conv_names[key]
+            if name == "conv1_1":
+                w = self.conv1_1.weight
+                wt = self._cache.get("vgg_bwd.conv1_1" + (":pre" if preprocess else ""), w,
+                                     lambda w: vgg_bwd_weight_conv1(w, preprocess))
+                return ops.vgg_conv1_bwd(dZ, wt)
+            wt = self._cache.get("vgg_bwd." + name + ":wt", getattr(self, name).weight, vgg_bwd_weight)
+            g = ops.conv3x3(dZ, wt, self._bwd_packs(name), None, layer="vgg_bwd." + name)
+            del dZ
+            i -= 1
+        return None
+
+    def _forward(self, x, out_keys, preprocess, _gray, saved=None):
+        """The layer walk.  saved: a dict that receives every convolution's post-ReLU output (the full-resolution tensor of a
+        pool-fused layer too) — the backward's masks and routes."""
         x = x.detach().float() if _gray else x.detach().contiguous().float()
         N = x.shape[0]
         for k in out_keys:
@@ -209,7 +310,8 @@ class VGG19_pytorch(nn.Module):
                     ops.layer_record.append(dict(layer="vgg." + conv_names[key], Cin=cur.shape[1], Cout=conv.weight.shape[0],
                                                  H=cur.shape[2], W=cur.shape[3], dil=1, in_up=1, in_sub=1, eligible=True))
                 cur, pooled = ops.conv2d_winograd_pool(cur, _packs(self._cache, conv_names[key], conv.weight)("winograd"),
-                                                       conv.bias.detach(), act=ops.ACT_RELU, want_full=key in out_keys)
+                                                       conv.bias.detach(), act=ops.ACT_RELU,
+                                                       want_full=key in out_keys or saved is not None)
             else:
                 name = conv_names[key]
                 conv = getattr(self, name)
@@ -223,6 +325,8 @@ class VGG19_pytorch(nn.Module):
                     cur = ops.conv3x3(cur, conv.weight, _packs(self._cache, name, conv.weight), bias, act=ops.ACT_RELU,
                                       layer="vgg." + name)
             out[key] = cur
+            if saved is not None and key[0] == "r":
+                saved[key] = cur
         return [out[key] for key in out_keys]
 
 

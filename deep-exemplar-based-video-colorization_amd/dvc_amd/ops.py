@@ -1011,6 +1011,60 @@ def lab2rgb(lab, l_offset=0.0):
     return y
 
 
+def lab2rgb_bwd(lab, grad_rgb, l_offset=0.0):
+    """dvc_lab2rgb_bwd: d loss / d lab of lab2rgb(lab, l_offset) for d loss / d rgb = grad_rgb."""
+    lib = _lib.load()
+    _need(lab, "lab")
+    _need(grad_rgb, "grad_rgb")
+    N, C, H, W = lab.shape
+    assert C == 3 and grad_rgb.shape == lab.shape, (lab.shape, grad_rgb.shape)
+    g = torch.empty_like(lab)
+    _lib.check(lib.dvc_lab2rgb_bwd(_p(lab), N, H * W, float(l_offset), _p(grad_rgb), _p(g), _stream()), "dvc_lab2rgb_bwd")
+    return g
+
+
+# ---- VGG19 input gradient (csrc/vgg_bwd.hip; dvc_amd/nets.py walks the layers)
+def vgg_act_bwd(dX, g, R, out=None):
+    """dvc_vgg_act_bwd: (dX + g) * [R > 0]; dX or g may be None (not both).  `out` may be dX (in place)."""
+    lib = _lib.load()
+    for t, nm in ((dX, "dX"), (g, "g"), (R, "R"), (out, "out")):
+        _need(t, nm)
+    for t in (dX, g, out):
+        assert t is None or t.shape == R.shape, (None if t is None else t.shape, R.shape)
+    if out is None:
+        out = torch.empty_like(R)
+    _lib.check(lib.dvc_vgg_act_bwd(_p(dX), _p(g), _p(R), R.numel(), _p(out), _stream()), "dvc_vgg_act_bwd")
+    return out
+
+
+def vgg_pool_act_bwd(dP, gP, gR, R, avg=False):
+    """dvc_vgg_pool_act_bwd: (route(dP + gP) + gR) * [R > 0] through a 2x2 max (avg=False) or average pool of R [N,C,H,W];
+    dP, gP: [N,C,H//2,W//2].  Any of dP, gP, gR may be None (not all three)."""
+    lib = _lib.load()
+    for t, nm in ((dP, "dP"), (gP, "gP"), (gR, "gR"), (R, "R")):
+        _need(t, nm)
+    N, C, H, W = R.shape
+    for t in (dP, gP):
+        assert t is None or tuple(t.shape) == (N, C, H // 2, W // 2), (t.shape, R.shape)
+    assert gR is None or gR.shape == R.shape, (gR.shape, R.shape)
+    out = torch.empty_like(R)
+    _lib.check(lib.dvc_vgg_pool_act_bwd(_p(dP), _p(gP), _p(gR), _p(R), N * C, H, W, 1 if avg else 0, _p(out), _stream()),
+               "dvc_vgg_pool_act_bwd")
+    return out
+
+
+def vgg_conv1_bwd(dZ, w_t):
+    """dvc_vgg_conv1_bwd: the 3-channel input gradient of a 3x3 pad-1 convolution; w_t [3][C][3][3] (nets.vgg_bwd_weight_conv1)."""
+    lib = _lib.load()
+    _need(dZ, "dZ")
+    _need(w_t, "w_t")
+    N, C, H, W = dZ.shape
+    assert tuple(w_t.shape) == (3, C, 3, 3), (w_t.shape, dZ.shape)
+    dx = torch.empty((N, 3, H, W), device=dZ.device, dtype=torch.float32)
+    _lib.check(lib.dvc_vgg_conv1_bwd(_p(dZ), _p(w_t), N, C, H, W, _p(dx), _stream()), "dvc_vgg_conv1_bwd")
+    return dx
+
+
 # the merge of the correlation's partial softmax states folded into its consumer (pack_color_input): DVC_FOLD_MERGE=0 / set_fold_merge
 _fold_merge = _os.environ.get("DVC_FOLD_MERGE", "1") == "1"
 

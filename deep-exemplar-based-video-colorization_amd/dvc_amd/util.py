@@ -1,7 +1,7 @@
 """Tensor helpers on the hot path, HIP-backed (mirror of the ★ rows of /root/reference/utils/util.py).
 
-Only the functions the inference path uses are provided; host I/O, plotting and
-training-loss helpers of the reference's util.py are out of scope.
+Only the functions the inference path uses are provided, tensor_lab2rgb with its gradient for the
+training losses; host I/O, plotting and training-loss helpers of the reference's util.py are out of scope.
 """
 import torch
 
@@ -61,8 +61,26 @@ def vgg_preprocess(tensor):
     return y[:, 0:3].contiguous()
 
 
+class _Lab2RGB(torch.autograd.Function):
+    """tensor_lab2rgb with its gradient (train.py:649-668 trains through it): forward ops.lab2rgb, backward ops.lab2rgb_bwd."""
+
+    @staticmethod
+    def forward(ctx, lab):
+        lab = lab.detach().contiguous().float()
+        ctx.save_for_backward(lab)
+        return ops.lab2rgb(lab)
+
+    @staticmethod
+    def backward(ctx, grad_rgb):
+        lab, = ctx.saved_tensors
+        return ops.lab2rgb_bwd(lab, grad_rgb.contiguous())
+
+
 def tensor_lab2rgb(input):
-    """utils/util.py:379-414 — n x 3 x h x w Lab (L in [0,100]) -> sRGB [0,1]."""
+    """utils/util.py:379-414 — n x 3 x h x w Lab (L in [0,100]) -> sRGB [0,1].  Differentiable when the input requires grad
+    under grad mode (the gradient of the reference's composition, ATen's rules: dvc_lab2rgb_bwd)."""
     if not input.is_cuda:
         raise RuntimeError("tensor_lab2rgb: the HIP path has no CPU fallback")
+    if input.requires_grad and torch.is_grad_enabled():
+        return _Lab2RGB.apply(input)
     return ops.lab2rgb(input.detach().contiguous().float())

@@ -495,6 +495,30 @@ int dvc_nlwa_fwd(const float* x_lab, int32_t Cx, int32_t Hx, int32_t Wx, const f
                  int32_t B, int32_t H, int32_t W, float scale_xh, float scale_xw, float scale_fh, float scale_fw, int32_t patch_size,
                  float alpha, float* out, void* workspace, size_t workspace_bytes, dvcStream stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Input gradient of VGG19_pytorch (frozen weights) and of tensor_lab2rgb — csrc/vgg_bwd.hip.  The 3x3 convolutions' input
+ * gradients run on dvc_conv2d / dvc_conv2d_winograd / dvc_conv2d_ws with the transposed, flipped filters; these are the steps
+ * between them.  Masks and routes follow ATen: threshold_backward(grad, relu_out, 0) zeroes the gradient where out <= 0;
+ * max_pool2d sends a window's gradient to the first maximum in scan order (a NaN takes the window).  Deterministic.
+ *
+ * dvc_vgg_act_bwd:  dZ = (dX + g) * [R > 0] over n elements; dX or g may be NULL (not both; one alone passes unchanged).  dZ
+ *   may be dX (in place), not R or g.
+ * dvc_vgg_pool_act_bwd:  a 2x2 stride-2 pool (floor mode) between two layers, per plane [H][W] (R, gR, dZ) and [H/2][W/2]
+ *   (dP, gP):  dZ = (route(dP + gP) + gR) * [R > 0], route = the arg-max (DVC_POOL_MAX) or a quarter to each element
+ *   (DVC_POOL_AVG).  Any of dP, gP, gR may be NULL (not all three).  With odd H or W the last row / column gets gR * mask.
+ * dvc_vgg_conv1_bwd:  dx[N][3][H][W] = zero-padded 3x3 convolution of dZ [N][C][H][W] with w_t [3][C][3][3] (OIHW); C % 8 == 0,
+ *   C <= 256.  VGG19's conv1_1: w_t = W^T flipped (x255 and the BGR swap of vgg_preprocess folded in when it applies).
+ * dvc_lab2rgb_bwd:  grad_lab [N][3][HW] of dvc_lab2rgb at lab (same l_offset) for grad_rgb [N][3][HW]: the forward's float
+ *   arithmetic recomputed, ATen's derivatives of the reference's composition (clamps pass inclusively). */
+#define DVC_POOL_MAX 0
+#define DVC_POOL_AVG 1
+int dvc_vgg_act_bwd(const float* dX, const float* g, const float* R, int64_t n, float* dZ, dvcStream stream);
+int dvc_vgg_pool_act_bwd(const float* dP, const float* gP, const float* gR, const float* R, int32_t planes, int32_t H, int32_t W,
+                         int32_t pool_mode, float* dZ, dvcStream stream);
+int dvc_vgg_conv1_bwd(const float* dZ, const float* w_t, int32_t N, int32_t C, int32_t H, int32_t W, float* dx, dvcStream stream);
+int dvc_lab2rgb_bwd(const float* lab, int32_t N, int32_t HW, float l_offset, const float* grad_rgb, float* grad_lab,
+                    dvcStream stream);
+
 #ifdef DVC_DEBUG
 /* ------------------------------------------------------------------------------------------------
  * Diagnostics for the timing probes under tools/ — ONLY in a -DDVC_DEBUG build (`make -C csrc DEBUG=1` ->
