@@ -126,6 +126,13 @@ SIGNATURES = {
     "dvc_vgg_pool_act_bwd": (ctypes.c_int, [_VP, _VP, _VP, _VP, c_i32, c_i32, c_i32, c_i32, _VP, _VP]),
     "dvc_vgg_conv1_bwd": (ctypes.c_int, [_VP, _VP, c_i32, c_i32, c_i32, c_i32, _VP, _VP]),
     "dvc_lab2rgb_bwd": (ctypes.c_int, [_VP, c_i32, c_i32, ctypes.c_float, _VP, _VP, _VP]),
+    "dvc_cvn_wgrad_splits": (ctypes.c_int, [c_i32, c_i32, c_i32, c_i32, c_i32]),
+    "dvc_cvn_wgrad": (ctypes.c_int, [_VP, _VP, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, _VP, ctypes.c_size_t, _VP,
+                                     _VP]),
+    "dvc_cvn_head_bwd_workspace_floats": (ctypes.c_size_t, [c_i32, c_i32, c_i32]),
+    "dvc_cvn_head_bwd": (ctypes.c_int, [_VP, _VP, _VP, _VP, c_i32, c_i32, c_i32, ctypes.c_float, _VP, _VP, ctypes.c_size_t, _VP,
+                                        _VP]),
+    "dvc_cvn_inorm_bwd": (ctypes.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, c_i32, c_i32, c_i32, c_i32, _VP, _VP, _VP, _VP]),
 }
 # diagnostics for tools/ (include/dvc_hip.h, last section): exported by the -DDVC_DEBUG build only
 DEBUG_SIGNATURES = {

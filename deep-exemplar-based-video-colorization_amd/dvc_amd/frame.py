@@ -55,8 +55,9 @@ def frame_colorization(IA_lab, IB_lab, IA_last_lab, features_B, vggnet, nonlocal
                        exemplar_cache=None):
     """models/FrameColor.py:41-67.  Returns (IA_ab_predict, nonlocal_BA_lab, features_A_gray).
 
-    `joint_training` only toggles autograd in the reference; this implementation is inference-only
-    and its outputs never carry autograd history."""
+    `joint_training` only toggles autograd in the reference; here VGG19 and WarpNet stay inference-only (their outputs
+    carry no history), and a `colornet` in training mode under grad mode returns an IA_ab_predict that carries the gradients
+    of its parameters (the train.py case; ColorVidNet's training path, dvc_amd/nets.py)."""
     IA_lab = IA_lab.detach().contiguous().float()
     IA_l = IA_lab[:, 0:1, :, :]
     if luminance_noise:
@@ -224,10 +225,11 @@ class ClipColorizer:
     def _chain(self, cin):
         """The ColorVidNet chain; in multi-reference mode the R recurrences advance in lock step as ONE batch, planned as a
         batch (DVC_CONV_BATCH_PLAN)."""
-        if self.n_refs > 1 or (self.batch_plan and cin.shape[0] > 1):
-            with ops.batch_plan(True):
-                return self.col(cin)
-        return self.col(cin)
+        with torch.no_grad():       # (inference-only whatever the module's mode: ColorVidNet's training path is never captured)
+            if self.n_refs > 1 or (self.batch_plan and cin.shape[0] > 1):
+                with ops.batch_plan(True):
+                    return self.col(cin)
+            return self.col(cin)
 
     def _install_cache(self, old, new):
         """Captured front ends read the exemplar cache at the addresses it had at capture time: a new exemplar of the same
@@ -336,7 +338,7 @@ class ClipColorizer:
         if (self.graph if graph is None else graph) and not self.batch_plan:      # (batch-planned launches: eager, as in clip())
             return self._frame_graph(IA_lab.detach().contiguous().float(),
                                      dict(IA_last_lab=IA_last_lab.detach().contiguous().float()))
-        with ops.batch_plan(self.batch_plan):       # (the plan clip() runs under: the two APIs of one object agree bit for bit)
+        with ops.batch_plan(self.batch_plan), torch.no_grad():   # (the plan clip() runs under: the two APIs agree bit for bit)
             ab, nl, _ = frame_colorization(IA_lab, self.IB_lab, IA_last_lab, self.features_B, self.vgg, self.warp,
                                            self.col, joint_training=False, feature_noise=0,
                                            temperature=self.temperature, exemplar_cache=self.ex_cache)

@@ -9,13 +9,14 @@ so `load_state_dict(torch.load(...))`, `.parameters()`, `.eval()`, `.cuda()` beh
 only* (they give the parameters their reference names); no torch.nn forward is ever called — every
 forward pass is a sequence of libdvc_hip.so kernel launches on the current stream.
 
-Inference only, with one exception: VGG19_pytorch gives the input gradient (frozen weights) that the reference's training
-losses need (train.py:649-668 take the perceptual and contextual losses on the features of the predicted frame); WarpNet and
-ColorVidNet outputs never carry autograd history (the rest of the training path, train.py:402-427, is out of scope —
-SURVEY.md §2 rows 12-13).
+Inference only, with two exceptions: VGG19_pytorch gives the input gradient (frozen weights) that the reference's training
+losses need (train.py:649-668 take the perceptual and contextual losses on the features of the predicted frame), and
+ColorVidNet in training mode (`colornet.train()`, grad mode on, the input or a parameter requiring grad) gives the gradients
+of all its parameters and of its input (train.py trains it).  WarpNet outputs never carry autograd history.
 """
 import torch
 import torch.nn as nn
+from torch.autograd.function import once_differentiable
 
 from . import arch, ops
 
@@ -134,10 +135,10 @@ def _check_input(x, name):
         # the reference would record an autograd graph here (train.py:402-427); this forward is
         # inference-only, so say so instead of silently returning a tensor without history
         raise NotImplementedError(
-            f"{name}: an input requires grad and autograd is enabled, but the HIP forward is inference-only "
-            "(no backward kernels). Call it under torch.no_grad() as test.py:83 does, or detach the input; "
-            "gradients exist for VGG19_pytorch.forward (input gradient, frozen weights), tensor_lab2rgb, the fused "
-            "correlation (dvc_amd.corr_autograd) and the contextual losses.")
+            f"{name}: an input requires grad and autograd is enabled, but this forward is inference-only. Call it under "
+            "torch.no_grad() as test.py:83 does, or detach the input; gradients exist for ColorVidNet in training mode "
+            "(`colornet.train()`: parameters and input), VGG19_pytorch.forward (input gradient, frozen weights), "
+            "tensor_lab2rgb, the fused correlation (dvc_amd.corr_autograd) and the contextual losses.")
 
 
 def vgg_bwd_weight(w):
@@ -581,6 +582,39 @@ class WarpNet(nn.Module):
 
 
 # ========================================================================================== ColorVidNet
+def cvn_bwd_weight(w, pad_to=None):
+    """The input-gradient filters of one of ColorVidNet's 3x3 layers (pad == dil, stride 1): W^T flipped, [Cin][Cout][3][3],
+    with dilation d the same convolution at dilation d.  pad_to: zero output channels appended up to that count (conv1_1.0's
+    7-channel input gradient runs as a 32-channel convolution whose first 7 channels are kept)."""
+    wt = vgg_bwd_weight(w)
+    if pad_to is not None and wt.shape[0] < pad_to:
+        wt = torch.cat((wt, wt.new_zeros((pad_to - wt.shape[0],) + tuple(wt.shape[1:]))), dim=0).contiguous()
+    return wt
+
+
+class _CVNTrain(torch.autograd.Function):
+    """ColorVidNet.forward with what the backward needs saved (ColorVidNet._forward(saved=...)); backward walks the layers in
+    reverse and returns d x (when x requires grad) and the gradient of every parameter that requires grad."""
+
+    @staticmethod
+    def forward(ctx, x, module, names, *params):
+        saved, rstd = {}, {}
+        ab = module._forward(x, saved=saved, rstd=rstd)
+        saved["ab"] = ab
+        ctx.module, ctx.names = module, names
+        ctx.saved_keys = tuple(saved) + tuple("rstd:" + k for k in rstd)
+        ctx.save_for_backward(*saved.values(), *rstd.values())
+        return ab
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_ab):
+        tensors = dict(zip(ctx.saved_keys, ctx.saved_tensors))
+        need = {n for n, flag in zip(ctx.names, ctx.needs_input_grad[3:]) if flag}
+        dx, grads = ctx.module._backward(tensors, g_ab.contiguous(), need, ctx.needs_input_grad[0])
+        return (dx, None, None) + tuple(grads.get(n) for n in ctx.names)
+
+
 class ColorVidNet(nn.Module):
     def __init__(self, ic):
         super().__init__()
@@ -685,7 +719,98 @@ class ColorVidNet(nn.Module):
 
     def forward(self, x):
         """ x: gray image (1 channel), ab(2 channel), ab_err, ba_err"""
+        if self.training and torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            return self._forward_with_grad(x)
         _check_input(x, "ColorVidNet")
+        return self._forward(x)
+
+    def _forward_with_grad(self, x):
+        """The training path (train.py: `colornet.train()`): output bit-identical to the no-grad forward, with a backward to every
+        parameter and to x."""
+        if not x.is_cuda:
+            _check_input(x, "ColorVidNet")
+        if x.dtype != torch.float32:
+            raise TypeError(f"ColorVidNet: the training path takes a float32 input (got {x.dtype})")
+        named = [(n, p) for n, p in self.named_parameters()]
+        for n, p in named:
+            if p.requires_grad and (not p.is_cuda or p.dtype != torch.float32):
+                raise RuntimeError(f"ColorVidNet: parameter {n} must be a float32 ROCm tensor for the training path")
+        return _CVNTrain.apply(x, self, tuple(n for n, _ in named), *(p for _, p in named))
+
+    def _bwd_packs(self, key, pad_to=None):
+        """kind -> packed input-gradient filters of a 3x3 layer (cvn_bwd_weight), in the module's cache under their own keys."""
+        w = self._mod(key).weight
+        ck = "cvn_bwd." + key
+
+        def get(kind):
+            if kind == "winograd":
+                return self._cache.get(ck + ":wino", w, lambda w: ops.pack_winograd_weight(cvn_bwd_weight(w, pad_to)))
+            if kind == "ws":
+                return self._cache.get(ck + ":ws", w, lambda w: ops.pack_ws_weight(cvn_bwd_weight(w, pad_to)))
+            return self._cache.get(ck, w, lambda w: ops.pack_conv_weight(cvn_bwd_weight(w, pad_to)))
+        return get
+
+    def _backward(self, t, g_ab, need, need_dx):
+        """Parameter gradients (names in `need`) and d x (need_dx) from the saved tensors `t` (ColorVidNet._forward(saved=...)):
+        the head on dvc_cvn_head_bwd, then CVN_CONVS in reverse — each layer's dZ (ReLU backward, or the InstanceNorm backward
+        that gathers the norm's consumers), its weight gradient on dvc_cvn_wgrad, its input gradient on the forward's engines
+        with W^T flipped (ops.conv3x3)."""
+        grads = {}
+        dZ, dW, db = ops.cvn_head_bwd(t["ab"], g_ab, self._out_weight(), t["c10_2"], slope=0.2)
+        k_ab = arch.CVN_OUT["key"]
+        if k_ab + ".weight" in need:
+            grads[k_ab + ".weight"] = dW
+        if k_ab + ".bias" in need:
+            grads[k_ab + ".bias"] = db
+        dZ_of = {"c10_2": dZ}
+        adder = {c["add"]: c["dst"] for c in arch.CVN_CONVS if c["add"] is not None}    # skip output -> the block it adds into
+        contrib = {}                                                                        # activation -> {kind: gradient}
+        dx = None
+        for c in reversed(arch.CVN_CONVS):
+            key, dst, src, pre = c["key"], c["dst"], c["src"], c["pre"]
+            if dst in dZ_of:
+                dZ = dZ_of[dst]
+            elif dst in adder:          # a skip convolution (no activation): the dZ of the block it adds into
+                dZ = dZ_of[adder[dst]]
+            else:
+                g = contrib.pop(dst)
+                if "raw" in g:
+                    dZ = ops.vgg_act_bwd(g["raw"], None, t[dst], out=g["raw"])
+                else:
+                    ss_key = next((e["ss"] for e in arch.CVN_CONVS if e["src"] == dst and e["pre"] == "norm_ss"), None)
+                    dZ, dss = ops.cvn_inorm_bwd(t["n:" + dst], t["rstd:" + dst], t[dst], g_full=g.get("full"), g_ss=g.get("ss"),
+                                                ss_w=self._ss_weight(ss_key) if ss_key else None, g_up=g.get("up"))
+                    if dss is not None and ss_key + ".weight" in need:
+                        grads[ss_key + ".weight"] = dss.view(-1, 1, 1, 1)
+                dZ_of[dst] = dZ
+            X = t[src] if pre is None else t["nss:" + src] if pre == "norm_ss" else t["n:" + src]
+            in_up = 2 if pre == "up" else 1
+            if key + ".weight" in need or key + ".bias" in need:
+                dW, db = ops.cvn_wgrad(dZ, X, dil=c["dil"], in_up=in_up)
+                if key + ".weight" in need:
+                    grads[key + ".weight"] = dW
+                if key + ".bias" in need:
+                    grads[key + ".bias"] = db
+            w = self._mod(key).weight
+            if src == "x":
+                if need_dx:
+                    cin = w.shape[1]
+                    pad_to = max(32, -(-cin // 32) * 32)
+                    wt = self._cache.get("cvn_bwd." + key + ":wt", w, lambda w: cvn_bwd_weight(w, pad_to))
+                    dx = ops.conv3x3(dZ, wt, self._bwd_packs(key, pad_to), None, dil=c["dil"], layer="cvn_bwd." + key)[:, :cin]
+                continue
+            wt = self._cache.get("cvn_bwd." + key + ":wt", w, cvn_bwd_weight)
+            gi = ops.conv3x3(dZ, wt, self._bwd_packs(key), None, dil=c["dil"], layer="cvn_bwd." + key)
+            kind = {None: "raw", "norm": "full", "norm_ss": "ss", "up": "up"}[pre]
+            assert kind not in contrib.get(src, {}), (src, kind)
+            contrib.setdefault(src, {})[kind] = gi
+        return dx, grads
+
+    def _forward(self, x, saved=None, rstd=None):
+        """The layer walk.  saved / rstd: dicts that receive what the backward needs (training path): every convolution's
+        post-activation output under its name, each InstanceNorm output under "n:" + source (the scaled stride-2 one under
+        "nss:" + source) and its per-plane 1/sigma in `rstd`.  The split-K reduce is then never deferred into a norm's launch
+        (bit-identical either way), so that every activation exists as a tensor."""
         x = x.detach().contiguous().float()
         acts = {"x": x}
         normed = {}
@@ -696,17 +821,29 @@ class ColorVidNet(nn.Module):
         both = {c["src"]: c["ss"] for c in arch.CVN_CONVS if c["pre"] == "norm_ss"}
         both = {k: v for k, v in both.items() if any(c["src"] == k and c["pre"] in ("norm", "up") for c in arch.CVN_CONVS)}
 
+        def rstd_buf(src, ss_key=None):
+            if saved is None:
+                return None
+            assert ss_key is None       # (the plane scale is rstd only without a channel scale)
+            a = acts[src]
+            rstd[src] = torch.empty(a.shape[0] * a.shape[1], device=a.device, dtype=torch.float32)
+            return rstd[src]
+
         def norm_of(src, ss_key=None):
             """InstanceNorm2d(src) [* the depthwise `_ss` weight, stride 2] as a tensor (ColorVidNet.py:85-94,12)."""
             k = (src, ss_key)
             if k not in normed:
                 if src in both:
                     normed[(src, None)], normed[(src, both[src])] = ops.instnorm_apply(
-                        acts[src], eps=1e-5, second=(ss_weight(both[src]), 2))
+                        acts[src], eps=1e-5, second=(ss_weight(both[src]), 2), scale_out=rstd_buf(src))
                 else:
                     normed[k] = ops.instnorm_apply(acts[src], eps=1e-5,
                                                    chan_scale=ss_weight(ss_key) if ss_key else None,
-                                                   sub=2 if ss_key else 1)
+                                                   sub=2 if ss_key else 1, scale_out=rstd_buf(src, ss_key))
+                if saved is not None:
+                    for (s_, k_), v in normed.items():
+                        if s_ == src:
+                            saved[("nss:" if k_ else "n:") + src] = v
             return normed[k]
 
         # activations that are only ever read through an InstanceNorm: normalised right after the convolution that
@@ -764,7 +901,8 @@ class ColorVidNet(nn.Module):
                 kw["residual"] = acts[c["add"]]
             dst = c["dst"]
             acts[dst] = ops.conv3x3(src, conv.weight, _packs(self._cache, c["key"], conv.weight), conv.bias.detach(),
-                                    defer_reduce=dst in norm_uses and dst not in raw_use, layer="cvn." + c["key"], **kw)
+                                    defer_reduce=dst in norm_uses and dst not in raw_use and saved is None, layer="cvn." + c["key"],
+                                    **kw)
             if dst in norm_uses:
                 if dst in both:
                     norm_of(dst)
@@ -772,4 +910,9 @@ class ColorVidNet(nn.Module):
                     for ss_key in dict.fromkeys(norm_uses[dst]):
                         norm_of(dst, ss_key)
         out = self._mod(arch.CVN_OUT["key"])
+        if saved is not None:
+            for c in arch.CVN_CONVS:
+                if c["act"] != "none":
+                    saved[c["dst"]] = acts[c["dst"]]
+            saved["x"] = x
         return ops.conv1x1_small(acts["c10_2"], self._out_weight(), out.bias.detach(), act=ops.ACT_TANH128)

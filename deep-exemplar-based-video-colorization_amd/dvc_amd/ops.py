@@ -885,11 +885,12 @@ def affine_act(x, scale, shift, *, residual=None, slope_t=None, up=1, rpad=0, ou
 
 
 def instnorm_apply(x, *, eps=1e-5, chan_scale=None, residual=None, slope_t=None, up=1, sub=1, rpad=0, out=None,
-                   out_batch_stride=0, second=None):
+                   out_batch_stride=0, second=None, scale_out=None):
     """InstanceNorm2d (no affine, biased variance) + optional depthwise scale / skip-add / PReLU / nearest
     upsample / stride-2 subsample / replicate row pad, in one launch; `out=x` normalises in place.
     `second=(chan_scale2, sub2)` also returns InstanceNorm(x) * chan_scale2 at stride sub2 (same statistics,
-    same launch): the call then returns (y, y2)."""
+    same launch): the call then returns (y, y2).  `scale_out` [N*C] receives the per-plane scale, rstd * chan_scale
+    (the training path of ColorVidNet keeps rstd for its backward)."""
     lib = _lib.load()
     part = x if isinstance(x, ConvPartials) else None
     if part is not None:
@@ -910,14 +911,20 @@ def instnorm_apply(x, *, eps=1e-5, chan_scale=None, residual=None, slope_t=None,
         y2 = torch.empty((N, C, (H + 1) // 2, (W + 1) // 2) if sub2 == 2 else (N, C, H, W), device=dev,
                          dtype=torch.float32)
     if part is not None:
+        assert scale_out is None, "scale_out: materialise the convolution's output first (defer_reduce=False)"
         _lib.check(lib.dvc_instnorm_apply_partials(ctypes.c_void_p(part.data_ptr()), part.S, _p(part.bias), part.act,
                                                    part.act_slope, _p(part.act_slope_t), _p(residual), _p(slope_t),
                                                    _p(chan_scale), float(eps), N, C, H, W, up, sub, rpad, 0, out_batch_stride,
                                                    _p(out), None, None, _p(cs2), sub2, _p(y2), _stream()),
                    "dvc_instnorm_apply_partials")
         return out if second is None else (out, y2)
+    shift_out = None
+    if scale_out is not None:
+        _need(scale_out, "scale_out")
+        assert scale_out.numel() == N * C, (scale_out.shape, N, C)
+        shift_out = torch.empty_like(scale_out)
     _lib.check(lib.dvc_instnorm_apply(_p(x), _p(residual), _p(slope_t), _p(chan_scale), float(eps), N, C, H, W, up,
-                                      sub, rpad, 0, 0, out_batch_stride, _p(out), None, None, _p(cs2), sub2,
+                                      sub, rpad, 0, 0, out_batch_stride, _p(out), _p(scale_out), _p(shift_out), _p(cs2), sub2,
                                       _p(y2), _stream()),
                "dvc_instnorm_apply")
     return out if second is None else (out, y2)
@@ -1063,6 +1070,69 @@ def vgg_conv1_bwd(dZ, w_t):
     dx = torch.empty((N, 3, H, W), device=dZ.device, dtype=torch.float32)
     _lib.check(lib.dvc_vgg_conv1_bwd(_p(dZ), _p(w_t), N, C, H, W, _p(dx), _stream()), "dvc_vgg_conv1_bwd")
     return dx
+
+
+# ---- ColorVidNet backward (csrc/cvn_bwd.hip; dvc_amd/nets.py walks the layers)
+def cvn_wgrad_splits(N, Cin, Cout, H, W):
+    """The default number of position slots dvc_cvn_wgrad splits a layer's sum over."""
+    return int(_lib.load().dvc_cvn_wgrad_splits(N, Cin, Cout, H, W))
+
+
+def cvn_wgrad(dZ, X, *, dil=1, in_up=1, splits=None):
+    """dvc_cvn_wgrad: (dW [Cout][Cin][3][3], db [Cout]) of a 3x3 pad == dil convolution from its output gradient dZ [N,Cout,H,W]
+    and its input X [N,Cin,H,W] (in_up = 2: the half-resolution map the layer reads through a nearest x2 upsample)."""
+    lib = _lib.load()
+    _need(dZ, "dZ")
+    _need(X, "X")
+    N, Cout, H, W = dZ.shape
+    Cin = X.shape[1]
+    assert X.shape[0] == N and tuple(X.shape[2:]) == (H // in_up, W // in_up), (X.shape, dZ.shape, in_up)
+    S = cvn_wgrad_splits(N, Cin, Cout, H, W) if splits is None else int(splits)
+    ld = Cout * Cin * 9 + Cout
+    part = torch.empty(S * ld, device=dZ.device, dtype=torch.float32)
+    out = torch.empty(ld, device=dZ.device, dtype=torch.float32)
+    _lib.check(lib.dvc_cvn_wgrad(_p(dZ), _p(X), N, Cin, Cout, H, W, dil, in_up, S, _p(part), part.numel(), _p(out), _stream()),
+               "dvc_cvn_wgrad")
+    return out[:Cout * Cin * 9].view(Cout, Cin, 3, 3), out[Cout * Cin * 9:]
+
+
+def cvn_head_bwd(ab, grad_ab, w_ab, R, slope=0.2):
+    """dvc_cvn_head_bwd: conv10_ab + tanh*128 backward.  ab: the saved output [N,2,H,W]; w_ab [2][C]; R: the saved post-leaky
+    input [N,C,H,W].  Returns (dZ of the layer in front [N,C,H,W], dW_ab [2,C,1,1], db_ab [2])."""
+    lib = _lib.load()
+    for t, nm in ((ab, "ab"), (grad_ab, "grad_ab"), (w_ab, "w_ab"), (R, "R")):
+        _need(t, nm)
+    N, C, H, W = R.shape
+    assert tuple(ab.shape) == (N, 2, H, W) and grad_ab.shape == ab.shape and tuple(w_ab.shape) == (2, C), (ab.shape, w_ab.shape)
+    dZ = torch.empty_like(R)
+    part = torch.empty(int(lib.dvc_cvn_head_bwd_workspace_floats(N, C, H * W)), device=R.device, dtype=torch.float32)
+    out = torch.empty(2 * C + 2, device=R.device, dtype=torch.float32)
+    _lib.check(lib.dvc_cvn_head_bwd(_p(ab), _p(grad_ab), _p(w_ab), _p(R), N, C, H * W, float(slope), _p(dZ), _p(part),
+                                    part.numel(), _p(out), _stream()), "dvc_cvn_head_bwd")
+    return dZ, out[:2 * C].view(2, C, 1, 1), out[2 * C:]
+
+
+def cvn_inorm_bwd(n, rstd, R, g_full=None, g_ss=None, ss_w=None, g_up=None):
+    """dvc_cvn_inorm_bwd: the gradient at the pre-norm layer's pre-activation, (dn -> dx) * [R > 0], with dn assembled from a
+    full-resolution consumer g_full, a stride-2 consumer g_ss of n * ss_w, and a nearest-x2 consumer g_up.  Returns
+    (dZ, d ss_w [C] or None)."""
+    lib = _lib.load()
+    for t, nm in ((n, "n"), (rstd, "rstd"), (R, "R"), (g_full, "g_full"), (g_ss, "g_ss"), (ss_w, "ss_w"), (g_up, "g_up")):
+        _need(t, nm)
+    N, C, H, W = n.shape
+    assert R.shape == n.shape and rstd.numel() == N * C
+    assert g_full is None or g_full.shape == n.shape
+    assert g_ss is None or tuple(g_ss.shape) == (N, C, (H + 1) // 2, (W + 1) // 2), g_ss.shape
+    assert g_up is None or tuple(g_up.shape) == (N, C, 2 * H, 2 * W), g_up.shape
+    dZ = torch.empty_like(n)
+    ss_part = ss_grad = None
+    if g_ss is not None:
+        assert ss_w is not None and ss_w.numel() == C
+        ss_part = torch.empty(N * C, device=n.device, dtype=torch.float32)
+        ss_grad = torch.empty(C, device=n.device, dtype=torch.float32)
+    _lib.check(lib.dvc_cvn_inorm_bwd(_p(n), _p(rstd), _p(R), _p(g_full), _p(g_ss), _p(ss_w), _p(g_up), N, C, H, W, _p(dZ),
+                                     _p(ss_part), _p(ss_grad), _stream()), "dvc_cvn_inorm_bwd")
+    return dZ, ss_grad
 
 
 # the merge of the correlation's partial softmax states folded into its consumer (pack_color_input): DVC_FOLD_MERGE=0 / set_fold_merge

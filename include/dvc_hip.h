@@ -519,6 +519,35 @@ int dvc_vgg_conv1_bwd(const float* dZ, const float* w_t, int32_t N, int32_t C, i
 int dvc_lab2rgb_bwd(const float* lab, int32_t N, int32_t HW, float l_offset, const float* grad_rgb, float* grad_lab,
                     dvcStream stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * ColorVidNet's backward (training mode) — csrc/cvn_bwd.hip.  The 3x3 input gradients run on the forward's engines with the
+ * transposed, flipped filters; these are the other steps.  Every sum has a fixed order: results are bit-deterministic.
+ *
+ * dvc_cvn_wgrad:  weight and bias gradient of a 3x3 convolution, pad == dil, stride 1, on v_mfma_f32_32x32x2_f32:
+ *   out[co][ci][ky][kx] = sum_{b,y,x} dZ[b][co][y][x] * X[b][ci][y+(ky-1)dil][x+(kx-1)dil]   (zero outside the H x W map),
+ *   then out[Cout*Cin*9 + co] = sum_{b,y,x} dZ[b][co][y][x].  dZ is [N][Cout][H][W]; X is the layer's input [N][Cin][H][W], or
+ *   with in_up = 2 the half-resolution map [N][Cin][H/2][W/2] read through nearest x2 indexing (H, W even).  The positions are
+ *   split over S slots (1 <= S <= 65535; dvc_cvn_wgrad_splits gives the default, 0 on bad sizes); part holds
+ *   S * (Cout*Cin*9 + Cout) floats of partial sums, added in slot order by a second launch.
+ * dvc_cvn_head_bwd:  conv10_ab (1x1, 2 outputs) + tanh*128 at the saved output ab [N][2][HW] for grad_ab [N][2][HW]:
+ *   dpre = grad_ab * 128 * (1 - (ab/128)^2);  dZ[N][C][HW] = (w_ab^T dpre) * (R > 0 ? 1 : slope), R the saved post-leaky input
+ *   [N][C][HW];  out[2][C] = sum dpre R^T, out[2C + o] = sum dpre_o.  w_ab is [2][C]; part holds
+ *   dvc_cvn_head_bwd_workspace_floats(N, C, HW) floats.
+ * dvc_cvn_inorm_bwd:  InstanceNorm (no affine) backward per [H][W] plane, n the saved output and rstd [N*C] its 1/sigma:
+ *   dn = g_full + [y, x even] ss_w[c] g_ss[y/2][x/2] + (2x2 sum of g_up at 2y, 2x);
+ *   dZ = rstd (dn - mean(dn) - n mean(dn n)) * [R > 0], R the producing layer's post-ReLU output.  g_full [N][C][H][W], g_ss
+ *   [N][C][ceil(H/2)][ceil(W/2)], g_up [N][C][2H][2W]: any may be NULL (not all three).  With g_ss, ss_part [N][C] receives
+ *   sum_{even y, x} n g_ss per plane and ss_grad [C] their sum over images (the `_ss` depthwise weights' gradient). */
+int dvc_cvn_wgrad_splits(int32_t N, int32_t Cin, int32_t Cout, int32_t H, int32_t W);
+int dvc_cvn_wgrad(const float* dZ, const float* X, int32_t N, int32_t Cin, int32_t Cout, int32_t H, int32_t W, int32_t dil,
+                  int32_t in_up, int32_t S, float* part, size_t part_floats, float* out, dvcStream stream);
+size_t dvc_cvn_head_bwd_workspace_floats(int32_t N, int32_t C, int32_t HW);
+int dvc_cvn_head_bwd(const float* ab, const float* grad_ab, const float* w_ab, const float* R, int32_t N, int32_t C, int32_t HW,
+                     float slope, float* dZ, float* part, size_t part_floats, float* out, dvcStream stream);
+int dvc_cvn_inorm_bwd(const float* n, const float* rstd, const float* R, const float* g_full, const float* g_ss, const float* ss_w,
+                      const float* g_up, int32_t N, int32_t C, int32_t H, int32_t W, float* dZ, float* ss_part, float* ss_grad,
+                      dvcStream stream);
+
 #ifdef DVC_DEBUG
 /* ------------------------------------------------------------------------------------------------
  * Diagnostics for the timing probes under tools/ — ONLY in a -DDVC_DEBUG build (`make -C csrc DEBUG=1` ->
