@@ -3,6 +3,7 @@
 // what is here is what those engines do not do:
 //   dvc_cvn_wgrad      dW[co][ci][ky][kx] = sum_{b,y,x} dZ[b,co,y,x] X[b,ci,y+(ky-1)d,x+(kx-1)d],  db[co] = sum dZ
 //                      on v_mfma_f32_32x32x2_f32 (exact fp32), positions split over workgroups, partials summed in slot order
+//                      (the slot sums and the bias sums run in double and are rounded once)
 //   dvc_cvn_head_bwd   conv10_ab (1x1, 2 outputs) + tanh*128: d c10_2 through the leaky mask, dW_ab, db_ab
 //   dvc_cvn_inorm_bwd  InstanceNorm backward with up to three consumers, the producing layer's ReLU mask, and the `_ss` weights'
 //                      gradient
@@ -13,12 +14,14 @@ namespace {
 
 // ------------------------------------------------------------------------------------------------ fixed-order slot sum
 // out[i] = part[0][i] + part[1][i] + ... + part[S-1][i]   (slot stride `ld` floats)
+// The running sum is a double, rounded once at the end: a layer at 216x384 has hundreds of slots, and an fp32 chain over them
+// put the bias gradients of the full-resolution layers at 5x what a float32 pairwise sum makes (tests/test_gpu_bwd_audit.py).
 __global__ __launch_bounds__(256) void sum_slots_kernel(const float* __restrict__ part, int S, long ld, long n,
                                                         float* __restrict__ out) {
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        float s = part[i];
-        for (int k = 1; k < S; ++k) s += part[(long)k * ld + i];
-        out[i] = s;
+        double s = part[i];
+        for (int k = 1; k < S; ++k) s += (double)part[(long)k * ld + i];
+        out[i] = (float)s;
     }
 }
 
@@ -65,7 +68,7 @@ __global__ __launch_bounds__(256) void wgrad_kernel(WgradArgs a) {
     for (int t = 0; t < 9; ++t)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-    float bacc = 0.f;
+    double bacc = 0.0;      // (db is a plain sum over every position of the slot: a double chain, rounded once per slot)
 
     const long HW = (long)a.H * a.W, XHW = (long)a.XH * a.XW;
     for (int c = c_beg; c < c_end; ++c) {
@@ -99,7 +102,7 @@ __global__ __launch_bounds__(256) void wgrad_kernel(WgradArgs a) {
         __syncthreads();
         if (do_bias && tid < kWgT) {
 #pragma unroll
-            for (int s = 0; s < kWgP; ++s) bacc += sZ[tid * kWgZs + s];
+            for (int s = 0; s < kWgP; ++s) bacc += (double)sZ[tid * kWgZs + s];
         }
         const float4* za = reinterpret_cast<const float4*>(sZ + (wco + l31) * kWgZs + hi * 8);
         const float4 z0 = za[0], z1 = za[1];
@@ -128,7 +131,7 @@ __global__ __launch_bounds__(256) void wgrad_kernel(WgradArgs a) {
             }
         }
     }
-    if (do_bias && tid < kWgT && co0 + tid < a.Cout) slot[(long)a.Cout * a.Cin * 9 + co0 + tid] = bacc;
+    if (do_bias && tid < kWgT && co0 + tid < a.Cout) slot[(long)a.Cout * a.Cin * 9 + co0 + tid] = (float)bacc;
 }
 
 // ------------------------------------------------------------------------------------------------ head backward
@@ -183,9 +186,9 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
         }
     }
     if (tid < 2) {
-        float s = 0.f;
-        for (int q = 0; q < kHdP; ++q) s += sd[tid][q];
-        slot[2 * C + tid] = s;
+        double s = 0.0;
+        for (int q = 0; q < kHdP; ++q) s += (double)sd[tid][q];
+        slot[2 * C + tid] = (float)s;
     }
 }
 

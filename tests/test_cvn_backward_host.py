@@ -12,6 +12,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from bwd_audit import ref_inorm_bwd as _inorm_bwd64      # (the float64 restatement of dvc_cvn_inorm_bwd; the audit uses it too)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ONE = ctypes.c_void_p(256)      # a non-null address that is never dereferenced: every call below fails validation first
 NEW = ["dvc_cvn_wgrad_splits", "dvc_cvn_wgrad", "dvc_cvn_head_bwd_workspace_floats", "dvc_cvn_head_bwd", "dvc_cvn_inorm_bwd"]
@@ -106,22 +108,6 @@ def test_transposed_filters_give_the_input_gradient(dil, in_up):
         assert torch.allclose(F.avg_pool2d(full, 2) * 4, gx, rtol=1e-12, atol=1e-12)
     padded = cvn_bwd_weight(w, pad_to=8)
     assert padded.shape == (8, Cout, 3, 3) and torch.equal(padded[:Cin], cvn_bwd_weight(w)) and not padded[Cin:].any()
-
-
-def _inorm_bwd64(n, rstd, R, g_full, g_ss, ss_w, g_up):
-    """The kernel's arithmetic (dvc_cvn_inorm_bwd) restated in float64."""
-    dn = torch.zeros_like(n)
-    if g_full is not None:
-        dn = dn + g_full
-    if g_ss is not None:
-        dn[:, :, ::2, ::2] += ss_w.view(1, -1, 1, 1) * g_ss
-    if g_up is not None:
-        dn = dn + F.avg_pool2d(g_up, 2) * 4
-    md = dn.mean((2, 3), keepdim=True)
-    mdn = (dn * n).mean((2, 3), keepdim=True)
-    dx = rstd * (dn - md - n * mdn) * (R > 0)
-    dss = (n[:, :, ::2, ::2] * g_ss).sum((0, 2, 3)) if g_ss is not None else None
-    return dx, dss
 
 
 @pytest.mark.parametrize("H,W", [(12, 16), (9, 7)])

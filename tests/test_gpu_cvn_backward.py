@@ -66,8 +66,12 @@ def test_training_output_bit_identical(hw, algo):
 
 
 # bounds at about twice the measured worst tensor (MI355X: 2.4e-6 at 48x80, 5.5e-4 at 216x384 — the larger maps of the
-# contractive set have more activations near a ReLU's kink, where fp32 and float64 masks part).  The plain seed-0 weights are
-# chaotic over 31 layers (an fp32 rounding of the forward moves the float64 gradient by percent): not a yardstick here.
+# contractive set have more activations near a ReLU's kink, where fp32 and float64 masks part).  The 1e-3 at 216x384 is a
+# measure of the CHAIN's conditioning over 31 layers, not of the kernels: tests/test_gpu_bwd_audit.py holds every single launch
+# of the same backward, at that size and with both weight sets, to the engines' own 2e-5 / 5e-5 and to float32-CPU yardsticks,
+# and this 48x80 case at 1e-5 pins the wiring between the launches (which does not depend on the size).  The plain seed-0
+# weights are chaotic over 31 layers (an fp32 rounding of the forward moves the float64 gradient by percent), so they are not
+# compared end to end; the audit covers every launch on them.
 @pytest.mark.parametrize("B,H,W,contractive,bound", [(2, 48, 80, True, 1e-5), (1, 216, 384, True, 1e-3)])
 def test_gradients_vs_float64(B, H, W, contractive, bound):
     from dvc_amd import synth
@@ -290,3 +294,115 @@ def test_double_backward_refused():
     gx = torch.autograd.grad(y.sum(), m.conv10_ab.weight, create_graph=True)[0]
     with pytest.raises(RuntimeError):
         gx.sum().backward()
+
+
+# ================================================================================================ kernel edges
+# Branches of csrc/cvn_bwd.hip that the cases above do not execute, each alone against float64 with the audit's measures
+# (tests/bwd_audit.py: whole tensor, per filter tap, worst output channel; bound max(1e-6, 4 x the same sum by float32 CPU
+# ATen), the rule test_gpu_bwd_audit.py applies to every launch of a real backward).
+def _audit_line(rec, case):
+    import bwd_audit as BA
+    from test_gpu_bwd_audit import report
+    rec["secs"] = 0.0
+    report(BA.line(rec, case))
+    assert BA.violations(rec) == [], BA.line(rec, case)
+
+
+WGRAD_EDGES = [
+    # N, Cin, Cout, H, W, dil, in_up, splits
+    (2, 16, 24, 6, 16, 1, 1, None), (2, 16, 24, 6, 32, 2, 1, 3), (2, 16, 24, 6, 48, 1, 2, None),    # W % 16 == 0: no ragged chunk
+    (2, 16, 24, 5, 3, 2, 1, 1), (2, 16, 24, 4, 2, 2, 2, None), (1, 8, 8, 7, 5, 2, 1, 2),              # window wider than the row
+    (1, 24, 16, 9, 21, 1, 1, None), (3, 24, 16, 9, 21, 2, 1, None), (3, 24, 16, 8, 22, 1, 2, 5),      # N = 1, N = 3
+    (1, 8, 16, 2, 5, 1, 1, 64), (1, 8, 16, 2, 5, 2, 1, 64),                                          # more slots than chunks
+    (2, 96, 40, 11, 19, 1, 1, None), (2, 96, 40, 11, 19, 2, 1, 4), (1, 70, 130, 6, 18, 1, 2, None),   # both tiles ragged
+]
+
+
+@pytest.mark.parametrize("N,Cin,Cout,H,W,dil,in_up,splits", WGRAD_EDGES)
+def test_wgrad_kernel_edges(N, Cin, Cout, H, W, dil, in_up, splits):
+    import bwd_audit as BA
+    from dvc_amd import ops
+    X = _g(30, (N, Cin, H // in_up, W // in_up))
+    dZ = _g(31, (N, Cout, H, W))
+    dW, db = ops.cvn_wgrad(dZ.cuda(), X.cuda(), dil=dil, in_up=in_up, splits=splits)
+    _audit_line(BA.audit_wgrad(dW.cpu(), db.cpu(), dZ, X, dil, in_up, layer=f"edge {Cin}->{Cout}"), f"wgrad N{N} S={splits}")
+    if splits == 64:        # nchunks = 2: every slot but two has an empty range and must contribute exact zeros
+        one = ops.cvn_wgrad(dZ.cuda(), X.cuda(), dil=dil, in_up=in_up, splits=2)
+        assert torch.equal(one[0], dW) and torch.equal(one[1], db)
+
+
+@pytest.mark.parametrize("N,Cin,Cout,H,W,dil,in_up", [
+    (1, 64, 64, 216, 384, 1, 1),        # wgrad_kernel<1, 1> (conv1_2)
+    (1, 512, 512, 27, 48, 2, 1),        # wgrad_kernel<2, 1> (conv5_x, conv6_x)
+    (1, 256, 128, 108, 192, 1, 2),      # wgrad_kernel<1, 2> (conv9_1.1)
+])
+def test_wgrad_kernel_production_shapes(N, Cin, Cout, H, W, dil, in_up):
+    """One production shape per template instance the network uses, with the default slot count (512 slots over 5184 chunks
+    for 64 -> 64 at 216x384), twice: bit-identical."""
+    import bwd_audit as BA
+    from dvc_amd import ops
+    X = _g(32, (N, Cin, H // in_up, W // in_up))
+    dZ = _g(33, (N, Cout, H, W))
+    S = ops.cvn_wgrad_splits(N, Cin, Cout, H, W)
+    dW, db = ops.cvn_wgrad(dZ.cuda(), X.cuda(), dil=dil, in_up=in_up)
+    again = ops.cvn_wgrad(dZ.cuda(), X.cuda(), dil=dil, in_up=in_up)
+    assert torch.equal(again[0], dW) and torch.equal(again[1], db)
+    _audit_line(BA.audit_wgrad(dW.cpu(), db.cpu(), dZ, X, dil, in_up, layer=f"production {Cin}->{Cout}"), f"wgrad {H}x{W} S={S}")
+
+
+@pytest.mark.parametrize("B,C,H,W", [
+    (2, 16, 16, 16), (1, 16, 32, 48),       # HW an exact multiple of 256: no ragged block
+    (2, 16, 5, 7), (1, 8, 1, 1),            # HW < 256: one partial block
+    (2, 6, 9, 31), (1, 130, 11, 25),        # C % 4 != 0 (waves take channels w, w + 4, ...)
+    (1, 128, 216, 384),                     # the production shape
+])
+def test_head_bwd_kernel_edges(B, C, H, W):
+    import bwd_audit as BA
+    from dvc_amd import ops
+    R = F.leaky_relu(_g(34, (B, C, H, W)), 0.2)
+    w = _g(35, (2, C)) * (0.1 if C > 8 else 0.3)
+    bias = _g(36, (2,))
+    ab = (torch.tanh(torch.einsum("oc,bchw->bohw", w, R) + bias.view(1, 2, 1, 1)) * 128).contiguous()
+    g = _g(37, (B, 2, H, W))
+    got = ops.cvn_head_bwd(ab.cuda(), g.cuda(), w.cuda().contiguous(), R.cuda(), slope=0.2)
+    _audit_line(BA.audit_head(tuple(t.cpu() for t in got), ab, g, w, R, 0.2), f"head B{B}")
+
+
+@pytest.mark.parametrize("B,C,H,W,kinds", [
+    (2, 5, 3, 5, ("full", "ss", "up")), (1, 3, 3, 5, ("ss",)), (1, 4, 2, 3, ("full", "up")),     # a plane below one pass of 512
+    (1, 3, 16, 32, ("up",)),                                                                          # exactly one pass
+    (1, 64, 216, 384, ("full", "ss", "up")),                                                          # a production plane
+])
+def test_inorm_bwd_kernel_edges(B, C, H, W, kinds):
+    import bwd_audit as BA
+    from dvc_amd import ops
+    a = torch.relu(_g(38, (B, C, H, W)) + 0.3)
+    n = F.instance_norm(a.double(), eps=1e-5).float()
+    rstd = (1 / torch.sqrt(a.double().var((2, 3), unbiased=False) + 1e-5)).float().reshape(-1)
+    gf = _g(39, (B, C, H, W)) if "full" in kinds else None
+    gs = _g(40, (B, C, (H + 1) // 2, (W + 1) // 2)) if "ss" in kinds else None
+    ssw = _g(41, (C,)) if "ss" in kinds else None
+    gu = _g(42, (B, C, 2 * H, 2 * W)) if "up" in kinds else None
+    cu = lambda t: None if t is None else t.cuda()
+    dZ, dss = ops.cvn_inorm_bwd(cu(n), cu(rstd), cu(a), g_full=cu(gf), g_ss=cu(gs), ss_w=cu(ssw), g_up=cu(gu))
+    _audit_line(BA.audit_inorm(dZ.cpu(), None if dss is None else dss.cpu(), n, rstd, a, gf, gs, ssw, gu, layer=f"edge C{C}"),
+                f"inorm B{B}")
+
+
+def test_wgrad_bias_sum_at_production_size():
+    """db over 2 x 216 x 384 positions and 512 slots with dZ = 1 + noise (every slot's sum positive: no cancellation to hide
+    behind).  The kernel keeps the bias sum of a slot and the sum over slots in double and rounds each once to fp32: two
+    roundings of at most 2^-24 = 6e-8 relative each, 1.2e-7 in the worst case; the bound is twice that, 2.5e-7.  The fp32 chains this
+    replaced (160-term chains per slot, then 512 slots in sequence) give 1e-6 here and put the bias gradients of conv1_1.0 /
+    conv1_1.2 over the audit's bound at 216x384 (test_gpu_bwd_audit.py)."""
+    import bwd_audit as BA
+    from dvc_amd import ops
+    N, Cin, Cout, H, W = 2, 8, 64, 216, 384
+    assert ops.cvn_wgrad_splits(N, Cin, Cout, H, W) == 512
+    dZ = _g(43, (N, Cout, H, W)) + 1.0
+    X = _g(44, (N, Cin, H, W))
+    dW, db = ops.cvn_wgrad(dZ.cuda(), X.cuda())
+    e = BA.relerr(db.cpu(), dZ.double().sum((0, 2, 3)))
+    print(f"db at 2x216x384, 512 slots: relerr {e:.2e}")
+    assert e <= 2.5e-7, e
+    _audit_line(BA.audit_wgrad(dW.cpu(), db.cpu(), dZ, X, 1, 1, layer="bias 8->64"), "wgrad bias sum")

@@ -253,3 +253,146 @@ def test_guards():
         m.forward_gray(torch.rand(1, 1, 32, 48, device="cuda", requires_grad=True), ["r12"])
     with torch.no_grad():
         assert not m(x, ["r12"])[0].requires_grad
+
+
+# ================================================================================================ kernel edges
+# Branches of csrc/vgg_bwd.hip that the cases above do not execute, or execute only under an end-to-end bound.
+@pytest.mark.parametrize("fold", [True, False], ids=["preprocess_fold", "plain"])
+@pytest.mark.parametrize("N", [1, 3])
+@pytest.mark.parametrize("H,W", [(216, 384), (45, 70), (16, 16), (1, 1), (17, 15)])
+@pytest.mark.parametrize("C", [64, 8, 256])
+def test_conv1_bwd_kernel_vs_float64(C, H, W, N, fold):
+    """dvc_vgg_conv1_bwd alone against float64 F.conv2d: C = 64 (production) and the limits the entry point accepts, whole
+    tiles, ragged tiles, one tile, one pixel; 2e-5 (576 fp32 terms in a fixed order: the direct engine's number), whole map,
+    border ring and interior alike."""
+    import bwd_audit as BA
+    from dvc_amd import nets, ops
+    from test_gpu_bwd_audit import report
+    g = torch.Generator().manual_seed(C + 7 * H + W)
+    w = torch.randn(C, 3, 3, 3, generator=g) / 27 ** 0.5
+    dZ = torch.randn(N, C, H, W, generator=g)
+    wt = nets.vgg_bwd_weight_conv1(w, preprocess=fold)
+    assert tuple(wt.shape) == (3, C, 3, 3)
+    if fold:
+        assert torch.equal(wt, w.transpose(0, 1).flip(2, 3).flip(0) * 255.0)
+    got = ops.vgg_conv1_bwd(dZ.cuda(), wt.cuda())
+    rec = BA.audit_conv1_bwd(got.cpu(), dZ, wt, layer=f"edge C{C} N{N}")
+    rec["secs"] = 0.0
+    report(BA.line(rec, "conv1_bwd " + ("fold" if fold else "plain")))
+    assert BA.violations(rec) == [], BA.line(rec)
+
+
+def _act_inputs(seed, n):
+    g = torch.Generator().manual_seed(seed)
+    R = torch.relu(torch.randint(-2, 4, (n,), generator=g).float() * 0.5)
+    return torch.randn(n, generator=g), torch.randn(n, generator=g), R
+
+
+def test_act_bwd_grid_wrap_bit_exact_vs_aten():
+    """More than 8192 blocks x 256 threads x 4 float4 pieces: the four-in-flight loop runs with every piece in range, then wraps
+    the capped grid (one [7, 64, 216, 384] buffer), in place and out of place."""
+    import bwd_audit as BA
+    from dvc_amd import ops
+    shape = (7, 64, 216, 384)
+    n = 7 * 64 * 216 * 384
+    assert n // 4 > 8192 * 256 * 4
+    free, _ = torch.cuda.mem_get_info()
+    if free < 5 * 4 * n:
+        pytest.skip(f"the card has {free >> 20} MiB free; this case holds four {4 * n >> 20} MiB buffers")
+    dX, gR, R = (t.view(shape) for t in _act_inputs(3, n))
+    want = BA.ref_act_bwd(dX, gR, R)
+    d, gg, r = dX.cuda(), gR.cuda(), R.cuda()
+    assert torch.equal(ops.vgg_act_bwd(d, gg, r).cpu(), want)
+    assert torch.equal(ops.vgg_act_bwd(d, gg, r, out=d).cpu(), want)
+    assert torch.equal(ops.vgg_act_bwd(None, gg, r).cpu(), BA.ref_act_bwd(None, gR, R))
+
+
+@pytest.mark.parametrize("n", [4096, 1003, 1, 5])
+def test_act_bwd_scalar_path_bit_exact_vs_aten(n):
+    """n % 4 != 0, and a 4-byte-offset view of each of dX, g, R and out in turn: the scalar kernel, the same bits."""
+    import bwd_audit as BA
+    from dvc_amd import ops
+    dX, gR, R = _act_inputs(4, n)
+    want = BA.ref_act_bwd(dX, gR, R)
+    assert torch.equal(ops.vgg_act_bwd(dX.cuda(), gR.cuda(), R.cuda()).cpu(), want)
+
+    def off(t):
+        buf = torch.zeros(n + 8, device="cuda")
+        v = buf[1:1 + n]
+        v.copy_(t)
+        assert v.data_ptr() % 16 == 4 and v.is_contiguous()
+        return buf, v
+    for which in range(4):
+        args = [dX.cuda(), gR.cuda(), R.cuda(), torch.full((n,), 7.0, device="cuda")]
+        buf, args[which] = off(args[which].cpu())
+        out = ops.vgg_act_bwd(args[0], args[1], args[2], out=args[3])
+        assert out is args[3] and torch.equal(out.cpu(), want), which
+        if which == 3:
+            assert buf[0] == 0 and bool((buf[1 + n:] == 0).all())       # nothing written around the view
+    _, d = off(dX)
+    assert torch.equal(ops.vgg_act_bwd(d, gR.cuda(), R.cuda(), out=d).cpu(), want)      # in place on the offset view
+
+
+NAN, INF = float("nan"), float("inf")
+
+
+@pytest.mark.parametrize("W", [8, 9])
+def test_pool_act_bwd_nan_windows_bit_exact_vs_aten(W):
+    """R with NaN in a window (one NaN, two NaNs, NaN beside +inf): ATen's scan `v > max || isnan(v)` gives the window to its LAST
+    NaN (tests/test_bwd_audit_host.py shows this ATen doing so on the CPU); float2 (W = 8) and scalar (W = 9) paths."""
+    import bwd_audit as BA
+    from dvc_amd import ops
+    g = torch.Generator().manual_seed(5)
+    R = torch.relu(torch.randint(-2, 4, (2, 3, 6, W), generator=g).float() * 0.5)
+    wins = [(1.0, NAN, 3.0, 2.0), (NAN, 1.0, NAN, 2.0), (1.0, NAN, 2.0, NAN), (NAN, INF, 0.5, 1.0), (INF, NAN, 0.5, 1.0),
+            (NAN, NAN, NAN, NAN)]
+    for i, wv in enumerate(wins):
+        y, x = 2 * (i // 3), 2 * (i % 3)
+        R[i % 2, i % 3, y:y + 2, x:x + 2] = torch.tensor(wv).view(2, 2)
+    dP, gP = torch.randn(2, 3, 3, W // 2, generator=g), torch.randn(2, 3, 3, W // 2, generator=g)
+    gR = torch.randn(R.shape, generator=g)
+    for use in ((1, 1, 1), (1, 0, 0), (0, 1, 1)):
+        a, b, c = (t if u else None for t, u in zip((dP, gP, gR), use))
+        want = BA.ref_pool_act_bwd(a, b, c, R)
+        assert torch.isfinite(want).all()
+        cu = lambda t: None if t is None else t.cuda()
+        got = ops.vgg_pool_act_bwd(cu(a), cu(b), cu(c), R.cuda())
+        assert torch.equal(got.cpu(), want), (W, use, (got.cpu() - want).abs().max())
+
+
+@pytest.mark.parametrize("pool", ["max", "avg"])
+def test_pool_act_bwd_offset_base_takes_the_scalar_path(pool):
+    """Even W with R (then gR) at a 4-byte offset from an 8-byte boundary: the scalar kernel, the same bits."""
+    import bwd_audit as BA
+    from dvc_amd import ops
+    N, C, H, W = 2, 3, 6, 10
+    z = _crafted(6, N, C, H, W)
+    R = torch.relu(z)
+    g = torch.Generator().manual_seed(7)
+    dP, gR = torch.randn(N, C, H // 2, W // 2, generator=g), torch.randn(N, C, H, W, generator=g)
+    want = BA.ref_pool_act_bwd(dP, None, gR, R, avg=pool == "avg")
+
+    def off(t):
+        v = torch.zeros(t.numel() + 3, device="cuda")[1:1 + t.numel()].view(t.shape)
+        v.copy_(t)
+        assert v.data_ptr() % 8 == 4
+        return v
+    for r, e in ((off(R), gR.cuda()), (R.cuda(), off(gR)), (off(R), off(gR))):
+        assert torch.equal(ops.vgg_pool_act_bwd(dP.cuda(), None, e, r, avg=pool == "avg").cpu(), want)
+
+
+@pytest.mark.parametrize("H,W", [(216, 384), (215, 384), (216, 383)])
+def test_pool_act_bwd_grid_wrap_bit_exact_vs_aten(H, W):
+    """More than 8192 blocks x 256 cells ([2, 64, 216, 384]): the capped grid wraps; odd H with even W and the reverse."""
+    import bwd_audit as BA
+    from dvc_amd import ops
+    N, C = 2, 64
+    assert N * C * ((H + 1) // 2) * ((W + 1) // 2) > 8192 * 256
+    z = _crafted(8, N, C, H, W)
+    R = torch.relu(z)
+    g = torch.Generator().manual_seed(9)
+    dP, gR = torch.randn(N, C, H // 2, W // 2, generator=g), torch.randn(N, C, H, W, generator=g)
+    for pool in ("max", "avg"):
+        want = BA.ref_pool_act_bwd(dP, None, gR, R, avg=pool == "avg")
+        got = ops.vgg_pool_act_bwd(dP.cuda(), None, gR.cuda(), R.cuda(), avg=pool == "avg")
+        assert torch.equal(got.cpu(), want), (pool, (got.cpu() - want).abs().max())
