@@ -133,6 +133,15 @@ SIGNATURES = {
     "dvc_cvn_head_bwd": (ctypes.c_int, [_VP, _VP, _VP, _VP, c_i32, c_i32, c_i32, ctypes.c_float, _VP, _VP, ctypes.c_size_t, _VP,
                                         _VP]),
     "dvc_cvn_inorm_bwd": (ctypes.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, c_i32, c_i32, c_i32, c_i32, _VP, _VP, _VP, _VP]),
+    "dvc_warp_up4_bwd": (ctypes.c_int, [_VP, c_i32, c_i32, c_i32, _VP, _VP]),
+    "dvc_warp_prelu_fwd": (ctypes.c_int, [_VP, _VP, _VP, c_i64, _VP, _VP]),
+    "dvc_warp_cn_bwd": (ctypes.c_int, [_VP, _VP, _VP, c_i32, c_i32, c_i32, ctypes.c_float, _VP, _VP]),
+    "dvc_warp_k1_wgrad_splits": (ctypes.c_int, [c_i32, c_i32, c_i32, c_i32]),
+    "dvc_warp_k1_wgrad": (ctypes.c_int, [_VP, _VP, c_i32, c_i32, c_i32, c_i32, c_i32, _VP, ctypes.c_size_t, _VP, _VP]),
+    "dvc_warp_norm_prelu_bwd": (ctypes.c_int, [_VP, _VP, _VP, _VP, _VP, c_i32, c_i32, c_i32, _VP, _VP, _VP, _VP]),
+    "dvc_warp_slope_sum": (ctypes.c_int, [_VP, c_i64, _VP, _VP]),
+    "dvc_warp_reflect_pad": (ctypes.c_int, [_VP, c_i32, c_i32, c_i32, _VP, _VP]),
+    "dvc_warp_fold": (ctypes.c_int, [_VP, _VP, c_i32, c_i32, c_i32, _VP, _VP]),
 }
 # diagnostics for tools/ (include/dvc_hip.h, last section): exported by the -DDVC_DEBUG build only
 DEBUG_SIGNATURES = {

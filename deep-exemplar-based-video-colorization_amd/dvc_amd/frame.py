@@ -10,6 +10,28 @@ from .util import feature_normalize, gray2rgb_batch
 VGG_OUT = ["r12", "r22", "r32", "r42", "r52"]
 
 
+def _warp_trains(nonlocal_net):
+    """True when this package's WarpNet would take its training path for the next call (dvc_amd/nets.py)."""
+    gate = getattr(nonlocal_net, "_takes_training_path", None)
+    return gate is not None and gate()
+
+
+class _PackColorInput(torch.autograd.Function):
+    """ops.pack_color_input with the gradient ColorVidNet's training path returns for its input handed on to WarpNet's outputs:
+    channels 1:3 of d color_input to the ab channels of the warped colour (its L channel is not read: zero), channel 3 to the
+    similarity map.  The frames are data."""
+
+    @staticmethod
+    def forward(ctx, warped_lab, sim, IA_lab, IA_last_lab):
+        return ops.pack_color_input(IA_lab, warped_lab.detach().contiguous(), sim.detach().contiguous(), IA_last_lab)
+
+    @staticmethod
+    def backward(ctx, g):
+        d_warped = torch.zeros((g.shape[0], 3) + tuple(g.shape[2:]), device=g.device, dtype=g.dtype)
+        d_warped[:, 1:3].copy_(g[:, 1:3])
+        return d_warped, g[:, 3:4].contiguous(), None, None
+
+
 def warp_color(IA_l, IB_lab, features_B, vggnet, nonlocal_net, colornet, feature_noise=0, temperature=0.01,
                exemplar_cache=None, defer_merge=False):
     """models/FrameColor.py:5-38.  `colornet` and `feature_noise` are unused there as well.
@@ -26,6 +48,13 @@ def warp_color(IA_l, IB_lab, features_B, vggnet, nonlocal_net, colornet, feature
     # NOTE: output the feature before normalization (FrameColor.py:13-14)
     features_A = [A_relu1_1, A_relu2_1, A_relu3_1, A_relu4_1, A_relu5_1]
     nA = ops.channel_l2norm_multi(features_A[1:])            # feature_normalize x4 (FrameColor.py:16-19), one launch
+    if _warp_trains(nonlocal_net):
+        # WarpNet's training path: the exemplar side is recomputed with history (no memo, no cache, no deferred merge)
+        if exemplar_cache is not None:
+            raise NotImplementedError("warp_color: `exemplar_cache` is not supported while nonlocal_net takes its training path")
+        nB = ops.channel_l2norm_multi((B_relu2_1, B_relu3_1, B_relu4_1, B_relu5_1))
+        nonlocal_BA_lab, similarity_map = nonlocal_net(IB_lab, *nA, *nB, temperature=temperature)
+        return nonlocal_BA_lab, similarity_map, features_A
     if exemplar_cache is None and ops.exemplar_memo_enabled() and hasattr(nonlocal_net, "_memo_exemplar_side"):
         # the reference's own call pattern (test.py:85-95: the same `IB_lab` / `features_B` objects every frame): the exemplar
         # side (FrameColor.py:20-23 + NonlocalNet.py:452-465,473-476,491-493) is computed on the first call and reused while
@@ -55,9 +84,10 @@ def frame_colorization(IA_lab, IB_lab, IA_last_lab, features_B, vggnet, nonlocal
                        exemplar_cache=None):
     """models/FrameColor.py:41-67.  Returns (IA_ab_predict, nonlocal_BA_lab, features_A_gray).
 
-    `joint_training` only toggles autograd in the reference; here VGG19 and WarpNet stay inference-only (their outputs
-    carry no history), and a `colornet` in training mode under grad mode returns an IA_ab_predict that carries the gradients
-    of its parameters (the train.py case; ColorVidNet's training path, dvc_amd/nets.py)."""
+    `joint_training` only toggles autograd in the reference; here VGG19 stays frozen (its features carry no history), a
+    `colornet` in training mode under grad mode returns an IA_ab_predict that carries the gradients of its parameters (the
+    train.py case; ColorVidNet's training path, dvc_amd/nets.py), and a `nonlocal_net` in training mode (heads frozen) then
+    receives, through the packed input, the gradients of its residual trunk and theta / phi projections as well."""
     IA_lab = IA_lab.detach().contiguous().float()
     IA_l = IA_lab[:, 0:1, :, :]
     if luminance_noise:
@@ -67,13 +97,17 @@ def frame_colorization(IA_lab, IB_lab, IA_last_lab, features_B, vggnet, nonlocal
         IA_lab_in = IA_lab
     # (the correlation's merge is folded into the launch that builds ColorVidNet's input, which also writes the warped Lab this
     # function returns: ops.pack_color_input(want_warped=True); modules that are not this package's WarpNet get the plain call)
-    fold = ops.fold_merge() and hasattr(nonlocal_net, "exemplar_side")
+    trains = _warp_trains(nonlocal_net)
+    fold = ops.fold_merge() and hasattr(nonlocal_net, "exemplar_side") and not trains
     nonlocal_BA_lab, similarity_map, features_A_gray = warp_color(
         IA_l, IB_lab, features_B, vggnet, nonlocal_net, colornet, feature_noise, temperature=temperature,
         exemplar_cache=exemplar_cache, defer_merge=fold)
     # cat((IA_l, nonlocal_BA_ab, similarity_map, IA_last_lab), dim=1)  (FrameColor.py:63-64)
-    color_input, nonlocal_BA_lab = ops.pack_color_input(IA_lab_in, nonlocal_BA_lab, similarity_map,
-                                                        IA_last_lab.detach().contiguous().float(), want_warped=True)
+    if trains:
+        color_input = _PackColorInput.apply(nonlocal_BA_lab, similarity_map, IA_lab_in, IA_last_lab.detach().contiguous().float())
+    else:
+        color_input, nonlocal_BA_lab = ops.pack_color_input(IA_lab_in, nonlocal_BA_lab, similarity_map,
+                                                            IA_last_lab.detach().contiguous().float(), want_warped=True)
     IA_ab_predict = colornet(color_input)
     return IA_ab_predict, nonlocal_BA_lab, features_A_gray
 

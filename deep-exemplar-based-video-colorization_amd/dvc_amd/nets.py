@@ -12,7 +12,9 @@ forward pass is a sequence of libdvc_hip.so kernel launches on the current strea
 Inference only, with two exceptions: VGG19_pytorch gives the input gradient (frozen weights) that the reference's training
 losses need (train.py:649-668 take the perceptual and contextual losses on the features of the predicted frame), and
 ColorVidNet in training mode (`colornet.train()`, grad mode on, the input or a parameter requiring grad) gives the gradients
-of all its parameters and of its input (train.py trains it).  WarpNet outputs never carry autograd history.
+of all its parameters and of its input (train.py trains it).  WarpNet in training mode (`nonlocal_net.train()`, grad mode on, a
+parameter of layer.* / theta / phi requiring grad, the four heads frozen) gives the gradients of its residual trunk and of the
+theta / phi projections; its heads and its inputs carry no history.
 """
 import torch
 import torch.nn as nn
@@ -137,8 +139,9 @@ def _check_input(x, name):
         raise NotImplementedError(
             f"{name}: an input requires grad and autograd is enabled, but this forward is inference-only. Call it under "
             "torch.no_grad() as test.py:83 does, or detach the input; gradients exist for ColorVidNet in training mode "
-            "(`colornet.train()`: parameters and input), VGG19_pytorch.forward (input gradient, frozen weights), "
-            "tensor_lab2rgb, the fused correlation (dvc_amd.corr_autograd) and the contextual losses.")
+            "(`colornet.train()`: parameters and input), WarpNet in training mode (`nonlocal_net.train()`: the residual trunk "
+            "and the theta / phi projections, heads frozen; its inputs are data), VGG19_pytorch.forward (input gradient, frozen "
+            "weights), tensor_lab2rgb, the fused correlation (dvc_amd.corr_autograd) and the contextual losses.")
 
 
 def vgg_bwd_weight(w):
@@ -332,6 +335,43 @@ class VGG19_pytorch(nn.Module):
 
 
 # ============================================================================================== WarpNet
+class _Up4(torch.autograd.Function):
+    """x4 nearest upsample (NonlocalNet.py:497-498) with its backward, the 4x4 block sum."""
+
+    @staticmethod
+    def forward(ctx, x):
+        return ops.upsample_nearest(x.detach().contiguous(), 4)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        return ops.warp_up4_bwd(g.contiguous())
+
+
+class _WarpTrain(torch.autograd.Function):
+    """WarpNet behind the trunk tensor — the residual blocks of both sides, the theta / phi projections, centre-and-normalise —
+    with what the backward needs saved (WarpNet._trunk_forward_saving); backward returns the gradient of every trunk / projection
+    parameter that requires grad and, when a trunk tensor requires grad, the gradient at the seam."""
+
+    @staticmethod
+    def forward(ctx, trunkA, trunkB, module, names, *params):
+        saved = {}
+        theta, phi = module._trunk_forward_saving(trunkA.detach(), trunkB.detach(), saved)
+        ctx.module, ctx.names = module, names
+        ctx.saved_keys = tuple(saved)
+        ctx.save_for_backward(*saved.values())
+        return theta, phi
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_theta, g_phi):
+        tensors = dict(zip(ctx.saved_keys, ctx.saved_tensors))
+        need = {n for n, flag in zip(ctx.names, ctx.needs_input_grad[4:]) if flag}
+        seam = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        dA, dB, grads = ctx.module._trunk_backward(tensors, g_theta, g_phi, need, need_trunk_input_grad=seam)
+        return (dA, dB, None, None) + tuple(grads.get(n) for n in ctx.names)
+
+
 class _ResidualBlockParams(nn.Module):
     """Parameter container with the reference's names (conv1, conv2, prelu), NonlocalNet.py:330-339."""
 
@@ -396,6 +436,10 @@ class WarpNet(nn.Module):
 
     def features(self, r2, r3, r4, r5):
         """Heads + concat + residual trunk for one side (NonlocalNet.py:451-465) -> [N,256,h,w]."""
+        return self._trunk(self._heads(r2, r3, r4, r5))
+
+    def _heads(self, r2, r3, r4, r5):
+        """The four heads of one side, concatenated: the `trunk` tensor [N,256,h,w] the residual blocks start from."""
         feats = [r2, r3, r4, r5]
         N = r2.shape[0]
         dev = r2.device
@@ -464,22 +508,182 @@ class WarpNet(nn.Module):
                                        rpad=rpad5 if hd["name"] == "layer5_1" else 0,
                                        out=trunk[:, hd["i"] * arch.WARP_FEATURE_CH:(hd["i"] + 1) * arch.WARP_FEATURE_CH],
                                        out_batch_stride=bs) for k, hd in enumerate(heads)])
-        x = trunk
+        return trunk
+
+    def _trunk(self, x, saved=None):
+        """The three residual blocks (NonlocalNet.py:341-352,464).  saved: a dict that receives what the backward needs (training
+        path) — per block b its input "x{b}", the two InstanceNorm outputs "n1.{b}" / "n2.{b}" with their per-plane 1/sigma
+        "rstd1.{b}" / "rstd2.{b}" and the first PReLU's output "p1.{b}".  The split-K reduce is then never deferred into a norm and
+        each PReLU is a launch of its own (ops.warp_prelu_fwd: the norm launch's own expression, bit-identical values), so that
+        every one of these exists as a tensor."""
         for b in range(arch.WARP_NUM_RESBLOCKS):
             blk = self.layer[b]
             a = blk.prelu.weight.detach()
+            if saved is not None:
+                planes = x.shape[0] * x.shape[1]
+                r1, r2 = (torch.empty(planes, device=x.device, dtype=torch.float32) for _ in range(2))
+                t = self._conv3(f"layer.{b}.conv1", blk.conv1, x, pad_mode=ops.PAD_REFLECT)
+                n1 = ops.instnorm_apply(t, out=t, scale_out=r1)
+                p1 = ops.warp_prelu_fwd(n1, a)
+                t = self._conv3(f"layer.{b}.conv2", blk.conv2, p1, pad_mode=ops.PAD_REFLECT)
+                n2 = ops.instnorm_apply(t, out=t, scale_out=r2)
+                saved.update({f"x{b}": x, f"n1.{b}": n1, f"rstd1.{b}": r1, f"p1.{b}": p1, f"n2.{b}": n2, f"rstd2.{b}": r2})
+                x = ops.warp_prelu_fwd(n2, a, skip=x)
+                continue
             t = self._conv3(f"layer.{b}.conv1", blk.conv1, x, pad_mode=ops.PAD_REFLECT, defer_reduce=True)
             t = _norm_in_place(t, slope_t=a)
             t = self._conv3(f"layer.{b}.conv2", blk.conv2, t, pad_mode=ops.PAD_REFLECT, defer_reduce=True)
             x = _norm_in_place(t, residual=x, slope_t=a)
         return x
 
-    def project(self, which, feats, bf16=False):
+    def project(self, which, feats, bf16=False, saved=None):
         """theta / phi: 1x1 conv, centre over positions, L2-normalise over channels -> [N,256,P]
-        (bf16=True: the ([N,P,256] fp32, [N,P,256] bf16) pair the bf16 correlation consumes)."""
+        (bf16=True: the ([N,P,256] fp32, [N,P,256] bf16) pair the bf16 correlation consumes).  saved: a dict that receives the
+        convolution's output "t.<which>" and its per-row means "mean.<which>" (training path, fp32 only)."""
         conv = getattr(self, which)
         t = ops.conv2d(feats, self._pk(which, conv), conv.bias.detach(), ksize=1, pad=0)
+        if saved is not None:
+            assert not bf16
+            out, mean = ops.corr_prepare_with_mean(t)
+            saved["t." + which], saved["mean." + which] = t, mean
+            return out
         return ops.corr_prepare_bf16(t) if bf16 else ops.corr_prepare(t)
+
+    # ---- the training path (train.py:402-427 trains nonlocal_net jointly with colornet): everything behind the trunk tensor
+    _HEADS = tuple(arch.WARP_HEAD_ORDER)
+
+    def _trunk_named_parameters(self):
+        """The 19 parameters behind the trunk tensor: layer.*, theta.*, phi.*."""
+        return [(n, p) for n, p in self.named_parameters() if n.split(".")[0] in ("layer", "theta", "phi")]
+
+    def _head_named_parameters(self):
+        return [(n, p) for n, p in self.named_parameters() if n.split(".")[0] in self._HEADS]
+
+    def _takes_training_path(self):
+        return self.training and torch.is_grad_enabled() and any(p.requires_grad for _, p in self._trunk_named_parameters())
+
+    def _check_training_call(self, exemplar_cache, return_taps, defer_merge, detach_flag):
+        unfrozen = [n for n, p in self._head_named_parameters() if p.requires_grad]
+        if unfrozen:
+            raise NotImplementedError(
+                f"WarpNet: the training path gives the gradients of the residual trunk and the theta / phi projections only "
+                f"(layer.*, theta.*, phi.*); {len(unfrozen)} head parameters require grad ({unfrozen[0]}, ...); freeze the heads: "
+                "`for head in (net.layer2_1, net.layer3_1, net.layer4_1, net.layer5_1): "
+                "[p.requires_grad_(False) for p in head.parameters()]`")
+        for flag, what in ((exemplar_cache is not None, "exemplar_cache"), (return_taps, "return_taps"), (defer_merge, "defer_merge"),
+                           (detach_flag, "detach_flag=True")):
+            if flag:
+                raise NotImplementedError(f"WarpNet: `{what}` is not supported on the training path (training mode, grad mode on, "
+                                          "a trunk / projection parameter requiring grad); call under torch.no_grad() or .eval()")
+
+    def _forward_with_grad(self, ins, temperature, WTA_scale_weight):
+        """(y, similarity_map) bit-identical to the no-grad forward on the fp32 correlation, with a backward to the trunk /
+        projection parameters.  The heads run as they do in inference, without history; the exemplar memo is neither read nor
+        filled."""
+        B_lab_map, A2, A3, A4, A5, B2, B3, B4, B5 = ins
+        fh, fw = int(B_lab_map.shape[2] / 4), int(B_lab_map.shape[3] / 4)
+        for n, p in self._trunk_named_parameters():
+            if p.requires_grad and (not p.is_cuda or p.dtype != torch.float32):
+                raise RuntimeError(f"WarpNet: parameter {n} must be a float32 ROCm tensor for the training path")
+        with torch.no_grad():
+            trunkA = self._heads(A2, A3, A4, A5)
+            trunkB = self._heads(B2, B3, B4, B5)
+            blab = ops.avgpool4x4(B_lab_map)
+        if (trunkA.shape[2], trunkA.shape[3]) != (fh, fw):
+            raise RuntimeError(f"shape '[{B_lab_map.shape[0]}, 1, {fh}, {fw}]' is invalid for feature map "
+                               f"of size {tuple(trunkA.shape[2:])}")
+        return self._train_from_trunks(trunkA, trunkB, blab, temperature, WTA_scale_weight)
+
+    def _train_from_trunks(self, trunkA, trunkB, blab, temperature, WTA_scale_weight=1):
+        """The differentiable part: trunk tensors [N,256,h,w] of both sides -> (y, similarity_map).  A trunk tensor that requires
+        grad gets its gradient too — the seam the heads' backward will start from (need_trunk_input_grad of _trunk_backward)."""
+        from .corr_autograd import fused_correlation
+        N, _, fh, fw = trunkA.shape
+        named = self._trunk_named_parameters()
+        theta, phi = _WarpTrain.apply(trunkA, trunkB, self, tuple(n for n, _ in named), *(p for _, p in named))
+        y, sim, _ = fused_correlation(theta, phi, blab.view(N, 3, -1), float(temperature), fh, fw, WTA_scale_weight)
+        return _Up4.apply(y), _Up4.apply(sim)
+
+    def _bwd_packs(self, key, conv):
+        """kind -> packed padded-input-gradient filters of a residual block's 3x3 layer (vgg_bwd_weight), under "warp_bwd." keys."""
+        w = conv.weight
+        ck = "warp_bwd." + key
+
+        def get(kind):
+            if kind == "winograd":
+                return self._cache.get(ck + ":wino", w, lambda w: ops.pack_winograd_weight(vgg_bwd_weight(w)))
+            if kind == "ws":
+                return self._cache.get(ck + ":ws", w, lambda w: ops.pack_ws_weight(vgg_bwd_weight(w)))
+            return self._cache.get(ck, w, lambda w: ops.pack_conv_weight(vgg_bwd_weight(w)))
+        return get
+
+    def _trunk_forward_saving(self, trunkA, trunkB, saved):
+        """Both sides as one batch of 2N images through the shared blocks, then theta on the A half and phi on the B half."""
+        N = trunkA.shape[0]
+        F = self._trunk(torch.cat((trunkA, trunkB), 0), saved=saved)
+        saved["F"] = F
+        return self.project("theta", F[:N], saved=saved), self.project("phi", F[N:], saved=saved)
+
+    def _trunk_backward(self, t, g_theta, g_phi, need, need_trunk_input_grad=False):
+        """Parameter gradients (names in `need`) from the saved tensors `t` (WarpNet._trunk(saved=...), project(saved=...)) and the
+        gradients at the centred, normalised theta / phi [N,256,P].  need_trunk_input_grad: also the gradient at the trunk
+        tensor of both sides, (dA, dB) — the seam; a normal training step skips that convolution.  Returns (dA, dB, grads)."""
+        grads = {}
+        F = t["F"]
+        M, C, h, w = F.shape
+        N = M // 2
+        dF = torch.empty_like(F)
+        need_blocks = need_trunk_input_grad or any(n.startswith("layer.") for n in need)
+        for which, g, sl in (("theta", g_theta, slice(0, N)), ("phi", g_phi, slice(N, M))):
+            conv = getattr(self, which)
+            dt = ops.warp_cn_bwd(t["t." + which], t["mean." + which], g.contiguous())
+            if which + ".weight" in need or which + ".bias" in need:
+                dW, db = ops.warp_k1_wgrad(dt, F[sl])
+                if which + ".weight" in need:
+                    grads[which + ".weight"] = dW
+                if which + ".bias" in need:
+                    grads[which + ".bias"] = db
+            if need_blocks:
+                wt = self._cache.get("warp_bwd." + which, conv.weight,
+                                     lambda w: ops.pack_conv_weight(w.detach().transpose(0, 1).contiguous()))
+                ops.conv2d(dt.view(N, -1, h, w), wt, None, ksize=1, pad=0, out=dF[sl])
+        if not need_blocks:
+            return None, None, grads
+        g = dF
+        for b in reversed(range(arch.WARP_NUM_RESBLOCKS)):
+            blk = self.layer[b]
+            a = blk.prelu.weight.detach()
+            pre = f"layer.{b}."
+            sp = torch.empty((2, M * C), device=F.device, dtype=torch.float64)
+            # second site: out = prelu(n2 + x)
+            dz, du, _ = ops.warp_norm_prelu_bwd(g, t[f"n2.{b}"], t[f"rstd2.{b}"], a, skip=t[f"x{b}"], slope_part=sp[0])
+            if pre + "conv2.weight" in need or pre + "conv2.bias" in need:
+                dW, db = ops.cvn_wgrad(dz, ops.warp_reflect_pad(t[f"p1.{b}"]))
+                if pre + "conv2.weight" in need:
+                    grads[pre + "conv2.weight"] = dW
+                if pre + "conv2.bias" in need:
+                    grads[pre + "conv2.bias"] = db
+            wt = self._cache.get(f"warp_bwd.layer.{b}.conv2:wt", blk.conv2.weight, vgg_bwd_weight)
+            gp = ops.conv3x3(dz, wt, self._bwd_packs(f"layer.{b}.conv2", blk.conv2), None, layer=f"warp_bwd.layer.{b}.conv2")
+            g = ops.warp_fold(gp)
+            del gp, dz
+            # first site: p1 = prelu(n1)
+            dz, _, _ = ops.warp_norm_prelu_bwd(g, t[f"n1.{b}"], t[f"rstd1.{b}"], a, slope_part=sp[1])
+            if pre + "conv1.weight" in need or pre + "conv1.bias" in need:
+                dW, db = ops.cvn_wgrad(dz, ops.warp_reflect_pad(t[f"x{b}"]))
+                if pre + "conv1.weight" in need:
+                    grads[pre + "conv1.weight"] = dW
+                if pre + "conv1.bias" in need:
+                    grads[pre + "conv1.bias"] = db
+            if pre + "prelu.weight" in need:
+                grads[pre + "prelu.weight"] = ops.warp_slope_sum(sp)
+            if b == 0 and not need_trunk_input_grad:
+                return None, None, grads
+            wt = self._cache.get(f"warp_bwd.layer.{b}.conv1:wt", blk.conv1.weight, vgg_bwd_weight)
+            gp = ops.conv3x3(dz, wt, self._bwd_packs(f"layer.{b}.conv1", blk.conv1), None, layer=f"warp_bwd.layer.{b}.conv1")
+            g = ops.warp_fold(gp, skip=du)
+            del gp, dz, du
+        return g[:N], g[N:], grads
 
     # ---- transparent exemplar memo (r05).  The reference's loop (test.py:68-96) hands the SAME exemplar tensors to every
     # frame_colorization call and NonlocalNet.py:452-465,473-476,491-493 recompute the exemplar side each time.  A caller that is
@@ -547,6 +751,9 @@ class WarpNet(nn.Module):
                B_relu5_1]
         for t in ins:
             _check_input(t, "WarpNet")
+        if self._takes_training_path():
+            self._check_training_call(exemplar_cache, return_taps, defer_merge, detach_flag)
+            return self._forward_with_grad([t.detach().contiguous().float() for t in ins], temperature, WTA_scale_weight)
         memo_key = (B_lab_map, B_relu2_1, B_relu3_1, B_relu4_1, B_relu5_1)      # (the caller's own tensor objects)
         ins = [t.detach().contiguous().float() for t in ins]
         B_lab_map, A2, A3, A4, A5, B2, B3, B4, B5 = ins

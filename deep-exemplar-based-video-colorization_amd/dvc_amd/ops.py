@@ -667,8 +667,17 @@ def conv3x3_group(items):
     def single(it, i=0):
         # (per-layer launches: the items' deferred partial sums must all be alive when the caller's next stage consumes them,
         # so every item but the first gets a convolution workspace of its own — same size, hence the same plan)
+        # (the first keeps the stream's own workspace unless a later item runs on the direct engine, which always uses — and so
+        # invalidates — that one: WarpNet's heads at 64x96, where layer3_1 is a Winograd layer and layer4_1 / layer5_1 are not)
         kw = {k: v for k, v in it.items() if k not in ("x", "weight", "packs", "bias")}
-        return conv3x3(it["x"], it["weight"], it["packs"], it["bias"], ws_tag="conv" if i == 0 else f"conv.g{i}", **kw)
+        own = i > 0 or not all(_item_is_winograd(o) for o in items[1:])
+        return conv3x3(it["x"], it["weight"], it["packs"], it["bias"], ws_tag=f"conv.g{i}" if own else "conv", **kw)
+
+    def _item_is_winograd(it):
+        N, Cin, H, W = it["x"].shape
+        dil = it.get("dil", 1)
+        return winograd_selected(N, Cin, H, W, it["weight"].shape[0], dil=dil, pad=dil, in_up=it.get("in_up", 1),
+                                 in_sub=it.get("in_sub", 1), layer=it.get("layer"))
 
     n = len(items)
     ok = _group_heads and 2 <= n <= 4
@@ -1133,6 +1142,132 @@ def cvn_inorm_bwd(n, rstd, R, g_full=None, g_ss=None, ss_w=None, g_up=None):
     _lib.check(lib.dvc_cvn_inorm_bwd(_p(n), _p(rstd), _p(R), _p(g_full), _p(g_ss), _p(ss_w), _p(g_up), N, C, H, W, _p(dZ),
                                      _p(ss_part), _p(ss_grad), _stream()), "dvc_cvn_inorm_bwd")
     return dZ, ss_grad
+
+
+# ---- WarpNet backward behind the trunk tensor (csrc/warp_bwd.hip; dvc_amd/nets.py walks the layers)
+def warp_up4_bwd(g):
+    """dvc_warp_up4_bwd: the 4x4 block sums of g [N,C,4h,4w] -> [N,C,h,w] (backward of the x4 nearest upsample)."""
+    lib = _lib.load()
+    _need(g, "g")
+    N, C, H, W = g.shape
+    if H % 4 or W % 4:
+        raise RuntimeError(f"dvc_amd: warp_up4_bwd: {H} x {W} is not a x4 upsampled map")
+    out = torch.empty((N, C, H // 4, W // 4), device=g.device, dtype=torch.float32)
+    _lib.check(lib.dvc_warp_up4_bwd(_p(g), N * C, H // 4, W // 4, _p(out), _stream()), "dvc_warp_up4_bwd")
+    return out
+
+
+def warp_prelu_fwd(n, slope_t, skip=None, out=None):
+    """dvc_warp_prelu_fwd: prelu(n + skip) with the one-element slope tensor `slope_t`; `out` may be n (in place)."""
+    lib = _lib.load()
+    for t, nm in ((n, "n"), (slope_t, "slope"), (skip, "skip"), (out, "out")):
+        _need(t, nm)
+    assert slope_t.numel() == 1 and (skip is None or skip.shape == n.shape) and (out is None or out.shape == n.shape)
+    if out is None:
+        out = torch.empty_like(n)
+    _lib.check(lib.dvc_warp_prelu_fwd(_p(n), _p(skip), _p(slope_t), n.numel(), _p(out), _stream()), "dvc_warp_prelu_fwd")
+    return out
+
+
+def corr_prepare_with_mean(t_raw, eps=EPS64):
+    """corr_prepare, also returning the per-(image, channel) means [B*C] the launch computes (the backward's centre)."""
+    lib = _lib.load()
+    _need(t_raw, "t_raw")
+    B, C = t_raw.shape[0], t_raw.shape[1]
+    P = t_raw[0, 0].numel()
+    out = torch.empty((B, C, P), device=t_raw.device, dtype=torch.float32)
+    mean = torch.empty(B * C, device=t_raw.device, dtype=torch.float32)
+    _lib.check(lib.dvc_corr_prepare(_p(t_raw), B, C, P, float(eps), _p(mean), _p(out), _stream()), "dvc_corr_prepare")
+    return out, mean
+
+
+def warp_cn_bwd(t_raw, mean, g, eps=EPS64):
+    """dvc_warp_cn_bwd: d t_raw of corr_prepare(t_raw) for d out = g [B,C,P]; mean from corr_prepare_with_mean."""
+    lib = _lib.load()
+    for t, nm in ((t_raw, "t_raw"), (mean, "mean"), (g, "g")):
+        _need(t, nm)
+    B, C = t_raw.shape[0], t_raw.shape[1]
+    P = t_raw[0, 0].numel()
+    assert tuple(g.shape) == (B, C, P) and mean.numel() == B * C, (t_raw.shape, g.shape, mean.shape)
+    dt = torch.empty((B, C, P), device=g.device, dtype=torch.float32)
+    _lib.check(lib.dvc_warp_cn_bwd(_p(t_raw), _p(mean), _p(g), B, C, P, float(eps), _p(dt), _stream()), "dvc_warp_cn_bwd")
+    return dt
+
+
+def warp_k1_wgrad_splits(N, Cin, Cout, P):
+    """The default number of position slots dvc_warp_k1_wgrad splits its sum over."""
+    return int(_lib.load().dvc_warp_k1_wgrad_splits(N, Cin, Cout, P))
+
+
+def warp_k1_wgrad(dT, F, *, splits=None):
+    """dvc_warp_k1_wgrad: (dW [Cout,Cin,1,1], db [Cout]) of a 1x1 convolution from its output gradient dT [N,Cout,P] (or
+    [N,Cout,h,w]) and its input F [N,Cin,P] (or [N,Cin,h,w])."""
+    lib = _lib.load()
+    _need(dT, "dT")
+    _need(F, "F")
+    N, Cout, Cin = dT.shape[0], dT.shape[1], F.shape[1]
+    P = dT[0, 0].numel()
+    assert F.shape[0] == N and F[0, 0].numel() == P, (dT.shape, F.shape)
+    S = warp_k1_wgrad_splits(N, Cin, Cout, P) if splits is None else int(splits)
+    ld = Cout * Cin + Cout
+    part = torch.empty(S * ld, device=dT.device, dtype=torch.float32)
+    out = torch.empty(ld, device=dT.device, dtype=torch.float32)
+    _lib.check(lib.dvc_warp_k1_wgrad(_p(dT), _p(F), N, Cin, Cout, P, S, _p(part), part.numel(), _p(out), _stream()),
+               "dvc_warp_k1_wgrad")
+    return out[:Cout * Cin].view(Cout, Cin, 1, 1), out[Cout * Cin:]
+
+
+def warp_norm_prelu_bwd(g, n, rstd, slope_t, skip=None, slope_part=None):
+    """dvc_warp_norm_prelu_bwd: from the gradient g [N,C,H,W] at prelu(n + skip), n an InstanceNorm output with 1/sigma rstd [N*C].
+    Returns (dz zero-ringed [N,C,H+2,W+2], du [N,C,H,W] — the skip's gradient, None without a skip —, slope_part [N*C] float64:
+    the slope gradient's per-plane partial sums; pass a preallocated slice as `slope_part`)."""
+    lib = _lib.load()
+    for t, nm in ((g, "g"), (n, "n"), (rstd, "rstd"), (slope_t, "slope"), (skip, "skip")):
+        _need(t, nm)
+    N, C, H, W = n.shape
+    assert g.shape == n.shape and rstd.numel() == N * C and slope_t.numel() == 1 and (skip is None or skip.shape == n.shape)
+    if slope_part is None:
+        slope_part = torch.empty(N * C, device=n.device, dtype=torch.float64)
+    if not (slope_part.is_cuda and slope_part.dtype == torch.float64 and slope_part.is_contiguous() and slope_part.numel() == N * C):
+        raise RuntimeError("dvc_amd: `slope_part` must be a contiguous float64 ROCm tensor of N*C elements")
+    dz = torch.empty((N, C, H + 2, W + 2), device=n.device, dtype=torch.float32)
+    du = torch.empty_like(n) if skip is not None else None
+    _lib.check(lib.dvc_warp_norm_prelu_bwd(_p(g), _p(n), _p(skip), _p(rstd), _p(slope_t), N * C, H, W, _p(dz), _p(du),
+                                           ctypes.c_void_p(slope_part.data_ptr()), _stream()), "dvc_warp_norm_prelu_bwd")
+    return dz, du, slope_part
+
+
+def warp_slope_sum(part):
+    """dvc_warp_slope_sum: the float64 partial sums `part` added in a fixed order -> a one-element float32 tensor."""
+    lib = _lib.load()
+    if not (isinstance(part, torch.Tensor) and part.is_cuda and part.dtype == torch.float64 and part.is_contiguous()):
+        raise RuntimeError("dvc_amd: `part` must be a contiguous float64 ROCm tensor")
+    out = torch.empty(1, device=part.device, dtype=torch.float32)
+    _lib.check(lib.dvc_warp_slope_sum(ctypes.c_void_p(part.data_ptr()), part.numel(), _p(out), _stream()), "dvc_warp_slope_sum")
+    return out
+
+
+def warp_reflect_pad(x):
+    """dvc_warp_reflect_pad: ReflectionPad2d(1) of x [N,C,H,W] -> [N,C,H+2,W+2]."""
+    lib = _lib.load()
+    _need(x, "x")
+    N, C, H, W = x.shape
+    xp = torch.empty((N, C, H + 2, W + 2), device=x.device, dtype=torch.float32)
+    _lib.check(lib.dvc_warp_reflect_pad(_p(x), N * C, H, W, _p(xp), _stream()), "dvc_warp_reflect_pad")
+    return xp
+
+
+def warp_fold(g_padded, skip=None):
+    """dvc_warp_fold: the adjoint of ReflectionPad2d(1) of g_padded [N,C,H+2,W+2] (+ skip [N,C,H,W]) -> [N,C,H,W]."""
+    lib = _lib.load()
+    _need(g_padded, "g_padded")
+    _need(skip, "skip")
+    N, C, PH, PW = g_padded.shape
+    H, W = PH - 2, PW - 2
+    assert skip is None or tuple(skip.shape) == (N, C, H, W), (g_padded.shape, skip.shape)
+    dx = torch.empty((N, C, H, W), device=g_padded.device, dtype=torch.float32)
+    _lib.check(lib.dvc_warp_fold(_p(g_padded), _p(skip), N * C, H, W, _p(dx), _stream()), "dvc_warp_fold")
+    return dx
 
 
 # the merge of the correlation's partial softmax states folded into its consumer (pack_color_input): DVC_FOLD_MERGE=0 / set_fold_merge

@@ -548,6 +548,44 @@ int dvc_cvn_inorm_bwd(const float* n, const float* rstd, const float* R, const f
                       const float* g_up, int32_t N, int32_t C, int32_t H, int32_t W, float* dZ, float* ss_part, float* ss_grad,
                       dvcStream stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * WarpNet's backward behind the trunk tensor (training mode) — csrc/warp_bwd.hip.  The residual blocks' 3x3 input gradients run
+ * on the forward's engines (zero pad 1 on a zero-ringed map, transposed flipped filters), their weight gradients on
+ * dvc_cvn_wgrad (zero-ringed dZ against a reflect-padded copy of the input); these are the other steps.  Every sum has a fixed
+ * order: results are bit-deterministic.
+ *
+ * dvc_warp_up4_bwd:  out[planes][h][w] = the 4x4 block sums of g [planes][4h][4w] (backward of the x4 nearest upsample).
+ * dvc_warp_prelu_fwd:  y = prelu(n + skip) over count elements (skip may be NULL; y may be n), slope read from device memory.
+ * dvc_warp_cn_bwd:  backward of dvc_corr_prepare at t_raw [B][C][P] with its per-row means mean [B][C]: tc = t - mean,
+ *   r = ||tc||_2 over channels, d tc = g / (r + eps) - tc (tc . g) / (r (r + eps)^2) (second term zero where r == 0), then
+ *   dt = d tc - mean_P(d tc) per channel row (channel sums and row means in double, rounded once).
+ * dvc_warp_k1_wgrad:  weight and bias gradient of a 1x1 convolution on v_mfma_f32_32x32x2_f32:
+ *   out[co][ci] = sum_{n,p} dT[n][co][p] F[n][ci][p], then out[Cout*Cin + co] = sum_{n,p} dT[n][co][p] (in double).  The positions
+ *   are split over S slots (1 <= S <= 65535; dvc_warp_k1_wgrad_splits gives the default, 0 on bad sizes); part holds
+ *   S * (Cout*Cin + Cout) floats of partial sums, added in slot order (in double) by a second launch.
+ * dvc_warp_norm_prelu_bwd:  per [H][W] plane, from the gradient g at a PReLU output whose input was u = n + skip (skip may be
+ *   NULL), n an InstanceNorm output with 1/sigma rstd [planes]:  du = g * (u > 0 ? 1 : a);  slope_part[plane] =
+ *   sum (u > 0 ? 0 : u g) (ATen's prelu backward);  dz = rstd (du - mean(du) - n mean(du n)) into the interior of the
+ *   zero-ringed plane dz_ringed [planes][H+2][W+2] (the ring is written too).  du [planes][H][W] (may be NULL) receives du, the
+ *   skip's gradient.
+ * dvc_warp_slope_sum:  out[0] = the sum of count doubles in a fixed order, rounded once.
+ * dvc_warp_reflect_pad:  x_padded [planes][H+2][W+2] = ReflectionPad2d(1) of x [planes][H][W]; H, W >= 2.
+ * dvc_warp_fold:  the adjoint: dx [planes][H][W] = the interior of g_padded [planes][H+2][W+2] + its ring folded onto rows /
+ *   columns 1 and H-2 / W-2 (+ skip [planes][H][W] when given; dx may be skip). */
+int dvc_warp_up4_bwd(const float* g, int32_t planes, int32_t h, int32_t w, float* out, dvcStream stream);
+int dvc_warp_prelu_fwd(const float* n, const float* skip, const float* slope, int64_t count, float* y, dvcStream stream);
+int dvc_warp_cn_bwd(const float* t_raw, const float* mean, const float* g, int32_t B, int32_t C, int32_t P, float eps, float* dt,
+                    dvcStream stream);
+int dvc_warp_k1_wgrad_splits(int32_t N, int32_t Cin, int32_t Cout, int32_t P);
+int dvc_warp_k1_wgrad(const float* dT, const float* F, int32_t N, int32_t Cin, int32_t Cout, int32_t P, int32_t S, float* part,
+                      size_t part_floats, float* out, dvcStream stream);
+int dvc_warp_norm_prelu_bwd(const float* g, const float* n, const float* skip, const float* rstd, const float* slope,
+                            int32_t planes, int32_t H, int32_t W, float* dz_ringed, float* du, double* slope_part,
+                            dvcStream stream);
+int dvc_warp_slope_sum(const double* part, int64_t count, float* out, dvcStream stream);
+int dvc_warp_reflect_pad(const float* x, int32_t planes, int32_t H, int32_t W, float* x_padded, dvcStream stream);
+int dvc_warp_fold(const float* g_padded, const float* skip, int32_t planes, int32_t H, int32_t W, float* dx, dvcStream stream);
+
 #ifdef DVC_DEBUG
 /* ------------------------------------------------------------------------------------------------
  * Diagnostics for the timing probes under tools/ — ONLY in a -DDVC_DEBUG build (`make -C csrc DEBUG=1` ->
