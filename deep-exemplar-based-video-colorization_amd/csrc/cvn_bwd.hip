@@ -8,28 +8,9 @@
 //   dvc_cvn_inorm_bwd  InstanceNorm backward with up to three consumers, the producing layer's ReLU mask, and the `_ss` weights'
 //                      gradient
 // Every sum has a fixed order: the results are bit-deterministic and do not depend on timing.
-#include "common.h"
+#include "bwd_common.h"
 
 namespace {
-
-// ------------------------------------------------------------------------------------------------ fixed-order slot sum
-// out[i] = part[0][i] + part[1][i] + ... + part[S-1][i]   (slot stride `ld` floats)
-// The running sum is a double, rounded once at the end: a layer at 216x384 has hundreds of slots, and an fp32 chain over them
-// put the bias gradients of the full-resolution layers at 5x what a float32 pairwise sum makes (tests/test_gpu_bwd_audit.py).
-__global__ __launch_bounds__(256) void sum_slots_kernel(const float* __restrict__ part, int S, long ld, long n,
-                                                        float* __restrict__ out) {
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        double s = part[i];
-        for (int k = 1; k < S; ++k) s += (double)part[(long)k * ld + i];
-        out[i] = (float)s;
-    }
-}
-
-static int launch_sum_slots(const float* part, int S, long ld, long n, float* out, hipStream_t st) {
-    const long blocks = cdivl(n, 256);
-    hipLaunchKernelGGL(sum_slots_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st, part, S, ld, n, out);
-    return 0;
-}
 
 // ------------------------------------------------------------------------------------------------ 3x3 weight gradient
 // Per tap this is a GEMM [Cout x P] . [P x Cin] whose operands are both contiguous along positions.  A workgroup owns a 64 (co) x
@@ -37,7 +18,7 @@ static int launch_sum_slots(const float* part, int S, long ld, long n, float* ou
 // dZ [64][16] and, for every (ci, ky, kx), the 16-position window of X that tap reads (zero outside the map; for in_up = 2 the
 // half-resolution map is read through nearest x2 indexing) into LDS, then each wave runs 9 taps x 8 MFMAs on its 32 x 32 quarter.
 // The K order inside a chunk is permuted (lane half h takes positions 8h..8h+7) so that both operands are float4 reads.
-constexpr int kWgT = 64;         // co / ci tile
+constexpr int kWgT = kWgTile;    // co / ci tile
 constexpr int kWgP = 16;         // positions per chunk
 constexpr int kWgZs = kWgP + 4;  // LDS row stride of dZ
 constexpr int kWgXs = 9 * kWgP + 4;  // LDS row stride (per ci) of the nine tap windows
@@ -59,10 +40,10 @@ __global__ __launch_bounds__(256) void wgrad_kernel(WgradArgs a) {
     const int l31 = lane & 31, hi = lane >> 5;
     const int ci0 = blockIdx.x * kWgT, co0 = blockIdx.y * kWgT, sp = blockIdx.z;
     const int wco = (wave & 1) * 32, wci = (wave >> 1) * 32;
-    const int c_beg = (int)((long)sp * a.nchunks / a.S), c_end = (int)((long)(sp + 1) * a.nchunks / a.S);
+    int c_beg, c_end;
+    wgrad_chunk_range(sp, a.nchunks, a.S, c_beg, c_end);
     const bool do_bias = blockIdx.x == 0;
 
-    typedef float f16v __attribute__((ext_vector_type(16)));
     f16v acc[9];
 #pragma unroll
     for (int t = 0; t < 9; ++t)
@@ -117,21 +98,9 @@ __global__ __launch_bounds__(256) void wgrad_kernel(WgradArgs a) {
         }
         __syncthreads();
     }
-    // C/D layout: column (ci) = lane & 31, row (co) = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
     float* slot = a.part + (long)sp * a.ld;
-    const int ci = ci0 + wci + l31;
-    if (ci < a.Cin) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int co = co0 + wco + (r & 3) + 8 * (r >> 2) + 4 * hi;
-            if (co < a.Cout) {
-                float* dst = slot + ((long)co * a.Cin + ci) * 9;
-#pragma unroll
-                for (int t = 0; t < 9; ++t) dst[t] = acc[t][r];
-            }
-        }
-    }
-    if (do_bias && tid < kWgT && co0 + tid < a.Cout) slot[(long)a.Cout * a.Cin * 9 + co0 + tid] = (float)bacc;
+    wgrad_store_tile<9>(slot, acc, ci0 + wci + l31, co0 + wco, hi, a.Cin, a.Cout);
+    wgrad_store_bias<9>(slot, do_bias, tid, co0, a.Cin, a.Cout, bacc);
 }
 
 // ------------------------------------------------------------------------------------------------ head backward
@@ -197,19 +166,6 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
 // dZ = rstd (dn - mean(dn) - n mean(dn n)) * [R > 0];  ss_part = sum_{even y, x} n g_ss.
 constexpr int kNbT = 512;
 
-__device__ __forceinline__ float block_sum(float v, float* red) {
-    // fixed order: butterfly inside each wave, then the waves' sums in wave order
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    __syncthreads();
-    if (lane == 0) red[wave] = v;
-    __syncthreads();
-    float s = red[0];
-    for (int k = 1; k < kNbT / 64; ++k) s += red[k];
-    return s;
-}
-
 __global__ __launch_bounds__(kNbT) void inorm_bwd_kernel(const float* __restrict__ n, const float* __restrict__ rstd,
                                                          const float* __restrict__ R, const float* __restrict__ gf,
                                                          const float* __restrict__ gs, const float* __restrict__ ssw,
@@ -247,10 +203,10 @@ __global__ __launch_bounds__(kNbT) void inorm_bwd_kernel(const float* __restrict
         sg = fmaf(nv, gsv, sg);
     }
     const float inv = 1.f / (float)HW;
-    const float md = block_sum(sd, red) * inv;
-    const float mdn = block_sum(sdn, red) * inv;
+    const float md = block_sum<float, kNbT>(sd, red) * inv;
+    const float mdn = block_sum<float, kNbT>(sdn, red) * inv;
     if (gsp) {
-        const float s = block_sum(sg, red);
+        const float s = block_sum<float, kNbT>(sg, red);
         if (threadIdx.x == 0) ss_part[plane] = s;
     }
     const float r = rstd[plane];
@@ -271,12 +227,7 @@ extern "C" int dvc_cvn_wgrad_splits(int32_t N, int32_t Cin, int32_t Cout, int32_
     if (N <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0) return 0;
     const long tiles = (long)cdiv(Cin, kWgT) * cdiv(Cout, kWgT);
     const long chunks = (long)N * H * cdiv(W, kWgP);
-    // about two workgroups per CU (256 CUs) and at least four chunks per workgroup
-    long s = cdivl(512, tiles);
-    const long cap = chunks / 4 > 1 ? chunks / 4 : 1;
-    if (s > cap) s = cap;
-    if (s > 65535) s = 65535;
-    return (int)(s < 1 ? 1 : s);
+    return wgrad_default_splits(tiles, chunks);
 }
 
 extern "C" int dvc_cvn_wgrad(const float* dZ, const float* X, int32_t N, int32_t Cin, int32_t Cout, int32_t H, int32_t W,
@@ -288,15 +239,10 @@ extern "C" int dvc_cvn_wgrad(const float* dZ, const float* X, int32_t N, int32_t
     DVC_REQUIRE(dil == 1 || dil == 2, "dvc_cvn_wgrad: dil must be 1 or 2 (got %d)", dil);
     DVC_REQUIRE(in_up == 1 || in_up == 2, "dvc_cvn_wgrad: in_up must be 1 or 2 (got %d)", in_up);
     DVC_REQUIRE(in_up == 1 || (H % 2 == 0 && W % 2 == 0), "dvc_cvn_wgrad: in_up = 2 needs even H and W");
-    DVC_REQUIRE(S >= 1 && S <= 65535, "dvc_cvn_wgrad: S must be in [1, 65535] (got %d)", S);
-    DVC_REQUIRE(Cout <= 65535 * kWgT && Cin <= 65535 * kWgT, "dvc_cvn_wgrad: too many channels");
     const int ncx = cdiv(W, kWgP);
     const long nchunks = (long)N * H * ncx;
-    DVC_REQUIRE(nchunks < (1L << 30), "dvc_cvn_wgrad: map too large");
     const long ld = (long)Cout * Cin * 9 + Cout;
-    DVC_REQUIRE(part_floats >= (size_t)S * ld, "dvc_cvn_wgrad: workspace too small (%zu floats, need %ld)", part_floats,
-                (long)S * ld);
-    DVC_REQUIRE(out != dZ && out != X && part != dZ && part != X && part != out, "dvc_cvn_wgrad: outputs must not alias inputs");
+    if (wgrad_check_frame("dvc_cvn_wgrad", S, Cin, Cout, nchunks, ld, dZ, X, part, part_floats, out)) return 1;
     WgradArgs a{dZ, X, part, N, Cin, Cout, H, W, H / in_up, W / in_up, ncx, (int)nchunks, S, ld};
     const dim3 grid(cdiv(Cin, kWgT), cdiv(Cout, kWgT), S);
     hipStream_t st = (hipStream_t)stream;

@@ -15,7 +15,7 @@
 // Every sum has a fixed order: the results are bit-deterministic and do not depend on timing.
 #include <cstdint>
 
-#include "common.h"
+#include "bwd_common.h"
 
 namespace {
 
@@ -87,44 +87,14 @@ __global__ __launch_bounds__(256) void cn_bwd_pos_kernel(const float* __restrict
         }
 }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
-// fixed order: butterfly inside each wave, then the waves' sums in wave order (NT threads)
-template <int NT>
-__device__ __forceinline__ double block_sum_f64(double v, double* red) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    v = wave_sum_f64(v);
-    __syncthreads();
-    if (lane == 0) red[wave] = v;
-    __syncthreads();
-    double s = red[0];
-    for (int k = 1; k < NT / 64; ++k) s += red[k];
-    return s;
-}
-
 // Step 2, per (image, channel) row: d t = d tc - mean_P(d tc), in place; the mean in double, rounded once.
 __global__ __launch_bounds__(256) void cn_bwd_center_kernel(float* __restrict__ d, int P) {
     __shared__ double red[4];
     float* row = d + (long)blockIdx.x * P;
     double s = 0.0;
     for (int i = threadIdx.x; i < P; i += 256) s += (double)row[i];
-    const float m = (float)(block_sum_f64<256>(s, red) / (double)P);
+    const float m = (float)(block_sum<double, 256>(s, red) / (double)P);
     for (int i = threadIdx.x; i < P; i += 256) row[i] -= m;
-}
-
-// ------------------------------------------------------------------------------------------------ fixed-order slot sum
-// out[i] = part[0][i] + ... + part[S-1][i], the running sum a double, rounded once (as csrc/cvn_bwd.hip)
-__global__ __launch_bounds__(256) void k1_sum_slots_kernel(const float* __restrict__ part, int S, long ld, long n,
-                                                           float* __restrict__ out) {
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        double s = part[i];
-        for (int k = 1; k < S; ++k) s += (double)part[(long)k * ld + i];
-        out[i] = (float)s;
-    }
 }
 
 // ------------------------------------------------------------------------------------------------ 1x1 weight gradient
@@ -132,7 +102,7 @@ __global__ __launch_bounds__(256) void k1_sum_slots_kernel(const float* __restri
 // contiguous range of 32-position chunks (never across two images); per chunk it stages dT [64][32] and F [64][32] in LDS and
 // each wave runs 16 MFMAs on its 32 x 32 quarter.  The K order inside a chunk is permuted (lane half h takes positions
 // 16h..16h+15) so that both operands are float4 reads, as dvc_cvn_wgrad does.
-constexpr int kK1T = 64;            // co / ci tile
+constexpr int kK1T = kWgTile;       // co / ci tile
 constexpr int kK1P = 32;            // positions per chunk
 constexpr int kK1S = kK1P + 4;      // LDS row stride
 
@@ -162,10 +132,10 @@ __global__ __launch_bounds__(256) void k1_wgrad_kernel(K1Args a) {
     const int l31 = lane & 31, hi = lane >> 5;
     const int ci0 = blockIdx.x * kK1T, co0 = blockIdx.y * kK1T, sp = blockIdx.z;
     const int wco = (wave & 1) * 32, wci = (wave >> 1) * 32;
-    const int c_beg = (int)((long)sp * a.nchunks / a.S), c_end = (int)((long)(sp + 1) * a.nchunks / a.S);
+    int c_beg, c_end;
+    wgrad_chunk_range(sp, a.nchunks, a.S, c_beg, c_end);
     const bool do_bias = blockIdx.x == 0;
 
-    typedef float f16v __attribute__((ext_vector_type(16)));
     f16v acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
@@ -198,17 +168,9 @@ __global__ __launch_bounds__(256) void k1_wgrad_kernel(K1Args a) {
         }
         __syncthreads();
     }
-    // C/D layout: column (ci) = lane & 31, row (co) = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
     float* slot = a.part + (long)sp * a.ld;
-    const int ci = ci0 + wci + l31;
-    if (ci < a.Cin) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int co = co0 + wco + (r & 3) + 8 * (r >> 2) + 4 * hi;
-            if (co < a.Cout) slot[(long)co * a.Cin + ci] = acc[r];
-        }
-    }
-    if (do_bias && tid < kK1T && co0 + tid < a.Cout) slot[(long)a.Cout * a.Cin + co0 + tid] = (float)bacc;
+    wgrad_store_tile<1>(slot, &acc, ci0 + wci + l31, co0 + wco, hi, a.Cin, a.Cout);
+    wgrad_store_bias<1>(slot, do_bias, tid, co0, a.Cin, a.Cout, bacc);
 }
 
 // ------------------------------------------------------------------------------------------------ PReLU + InstanceNorm backward
@@ -242,9 +204,9 @@ __global__ __launch_bounds__(kNpT) void norm_prelu_bwd_kernel(const float* __res
         sd += (double)du;
         sdn += (double)du * (double)nv;
     }
-    const float md = (float)(block_sum_f64<kNpT>(sd, red) / (double)HW);
-    const float mdn = (float)(block_sum_f64<kNpT>(sdn, red) / (double)HW);
-    const double sl = block_sum_f64<kNpT>(ss, red);
+    const float md = (float)(block_sum<double, kNpT>(sd, red) / (double)HW);
+    const float mdn = (float)(block_sum<double, kNpT>(sdn, red) / (double)HW);
+    const double sl = block_sum<double, kNpT>(ss, red);
     if (threadIdx.x == 0) slope_part[plane] = sl;
     const float r = rstd[plane];
     for (int i = threadIdx.x; i < PHW; i += kNpT) {
@@ -267,7 +229,7 @@ __global__ __launch_bounds__(256) void slope_sum_kernel(const double* __restrict
     __shared__ double red[4];
     double s = 0.0;
     for (long i = threadIdx.x; i < n; i += 256) s += part[i];
-    const double t = block_sum_f64<256>(s, red);
+    const double t = block_sum<double, 256>(s, red);
     if (threadIdx.x == 0) out[0] = (float)t;
 }
 
@@ -357,35 +319,23 @@ extern "C" int dvc_warp_k1_wgrad_splits(int32_t N, int32_t Cin, int32_t Cout, in
     if (N <= 0 || Cin <= 0 || Cout <= 0 || P <= 0) return 0;
     const long tiles = (long)cdiv(Cin, kK1T) * cdiv(Cout, kK1T);
     const long chunks = (long)N * cdiv(P, kK1P);
-    // about two workgroups per CU (256 CUs) and at least four chunks per workgroup
-    long s = cdivl(512, tiles);
-    const long cap = chunks / 4 > 1 ? chunks / 4 : 1;
-    if (s > cap) s = cap;
-    if (s > 65535) s = 65535;
-    return (int)(s < 1 ? 1 : s);
+    return wgrad_default_splits(tiles, chunks);
 }
 
 extern "C" int dvc_warp_k1_wgrad(const float* dT, const float* F, int32_t N, int32_t Cin, int32_t Cout, int32_t P, int32_t S,
                                  float* part, size_t part_floats, float* out, dvcStream stream) {
     DVC_REQUIRE(dT && F && part && out, "dvc_warp_k1_wgrad: null pointer");
     DVC_REQUIRE(N > 0 && Cin > 0 && Cout > 0 && P > 0, "dvc_warp_k1_wgrad: bad size (N %d Cin %d Cout %d P %d)", N, Cin, Cout, P);
-    DVC_REQUIRE(S >= 1 && S <= 65535, "dvc_warp_k1_wgrad: S must be in [1, 65535] (got %d)", S);
-    DVC_REQUIRE(Cout <= 65535 * kK1T && Cin <= 65535 * kK1T, "dvc_warp_k1_wgrad: too many channels");
     const int ncp = cdiv(P, kK1P);
     const long nchunks = (long)N * ncp;
-    DVC_REQUIRE(nchunks < (1L << 30), "dvc_warp_k1_wgrad: map too large");
     const long ld = (long)Cout * Cin + Cout;
-    DVC_REQUIRE(part_floats >= (size_t)S * ld, "dvc_warp_k1_wgrad: workspace too small (%zu floats, need %ld)", part_floats,
-                (long)S * ld);
-    DVC_REQUIRE(out != dT && out != F && part != dT && part != F && part != out, "dvc_warp_k1_wgrad: outputs must not alias inputs");
+    if (wgrad_check_frame("dvc_warp_k1_wgrad", S, Cin, Cout, nchunks, ld, dT, F, part, part_floats, out)) return 1;
     const int vec = P % 4 == 0 && ((reinterpret_cast<uintptr_t>(dT) | reinterpret_cast<uintptr_t>(F)) & 15) == 0;
     K1Args a{dT, F, part, N, Cin, Cout, P, ncp, (int)nchunks, S, vec, ld};
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k1_wgrad_kernel, dim3(cdiv(Cin, kK1T), cdiv(Cout, kK1T), S), dim3(256), 0, st, a);
     DVC_CHECK_LAUNCH("dvc_warp_k1_wgrad");
-    const long blocks = cdivl(ld, 256);
-    hipLaunchKernelGGL(k1_sum_slots_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st, part, (int)S, ld, ld,
-                       out);
+    launch_sum_slots(part, S, ld, ld, out, st);
     DVC_CHECK_LAUNCH("dvc_warp_k1_wgrad (slot sum)");
     return 0;
 }

@@ -23,6 +23,7 @@ from torch.autograd.function import once_differentiable
 from . import arch, ops
 
 _VGG_MEAN_BGR = (0.40760392, 0.45795686, 0.48501961)  # utils/util.py:351
+_VGG_CONV_OF = {("r%s" % n[4:].replace("_", "")): n for n, _, _ in arch.VGG_CONVS}     # output key "r12" -> "conv1_2"
 
 
 _pack_epoch = 0
@@ -101,15 +102,54 @@ def _same_tensors(a, b):
     return a == b
 
 
-def _packs(cache, key, weight):
-    """kind -> packed weight of one 3x3 layer: "direct" = [Cin][9][Cout], "winograd" = U = G g G^T (ops.conv3x3)."""
+def _packs(cache, key, weight, transform=None):
+    """kind -> packed weight of one 3x3 layer: "direct" = [Cin][9][Cout], "winograd" = U = G g G^T (ops.conv3x3).
+    transform: applied to the weight before it is packed (a backward walk's input-gradient filters)."""
     def get(kind):
         if kind == "winograd":
-            return cache.get(key + ":wino", weight, ops.pack_winograd_weight)
-        if kind == "ws":
-            return cache.get(key + ":ws", weight, ops.pack_ws_weight)
-        return cache.get(key, weight, ops.pack_conv_weight)
+            suffix, pack = ":wino", ops.pack_winograd_weight
+        elif kind == "ws":
+            suffix, pack = ":ws", ops.pack_ws_weight
+        else:
+            suffix, pack = "", ops.pack_conv_weight
+        return cache.get(key + suffix, weight, pack if transform is None else lambda w: pack(transform(w)))
     return get
+
+
+def _bwd_filters(cache, key, weight, transform):
+    """What ops.conv3x3 takes for a 3x3 layer's input gradient: (the transformed filters themselves, cached under key + ":wt",
+    and their `_packs` under key / key + ":wino" / key + ":ws").  key: "<net>_bwd.<layer>"; transform: vgg_bwd_weight or
+    cvn_bwd_weight (W^T flipped)."""
+    return cache.get(key + ":wt", weight, transform), _packs(cache, key, weight, transform)
+
+
+def _save_dict(ctx, tensors):
+    """Put a dict of tensors on an autograd ctx (save_for_backward); _saved_dict(ctx) gives it back in backward."""
+    ctx.saved_keys = tuple(tensors)
+    ctx.save_for_backward(*tensors.values())
+
+
+def _saved_dict(ctx):
+    return dict(zip(ctx.saved_keys, ctx.saved_tensors))
+
+
+def _wants(need, prefix):
+    """Is the weight or the bias gradient of the layer `prefix` asked for?"""
+    return prefix + ".weight" in need or prefix + ".bias" in need
+
+
+def _put_wb(grads, need, prefix, dW, db):
+    """Store dW / db under prefix.weight / prefix.bias, each only if its name is in `need`."""
+    for name, g in ((prefix + ".weight", dW), (prefix + ".bias", db)):
+        if name in need:
+            grads[name] = g
+
+
+def _check_trainable(named, who):
+    """The training paths launch on the parameters' storage: those that take a gradient are float32 ROCm tensors."""
+    for n, p in named:
+        if p.requires_grad and (not p.is_cuda or p.dtype != torch.float32):
+            raise RuntimeError(f"{who}: parameter {n} must be a float32 ROCm tensor for the training path")
 
 
 def _prepack(cache, key, conv):
@@ -167,19 +207,24 @@ class _VGGInputGrad(torch.autograd.Function):
         saved = {}
         outs = module._forward(x, out_keys, preprocess, False, saved=saved)
         ctx.module, ctx.out_keys, ctx.preprocess = module, tuple(out_keys), preprocess
-        ctx.saved_keys = tuple(saved)
-        ctx.save_for_backward(*saved.values())
+        _save_dict(ctx, saved)
         ctx.set_materialize_grads(False)
         return tuple(outs)
 
     @staticmethod
     def backward(ctx, *grads):
-        saved = dict(zip(ctx.saved_keys, ctx.saved_tensors))
+        saved = _saved_dict(ctx)
         g_ext = {k: g.contiguous() for k, g in zip(ctx.out_keys, grads) if g is not None}
         return ctx.module._input_grad(saved, g_ext, ctx.preprocess), None, None, None
 
 
 # ================================================================================================ VGG19
+def _check_vgg_keys(out_keys):
+    for k in out_keys:
+        if k not in arch.VGG_KEYS:
+            raise KeyError(k)
+
+
 class VGG19_pytorch(nn.Module):
     """NOTE: input tensor should range in [0,1] (RGB); see NonlocalNet.py:193-195."""
 
@@ -232,34 +277,18 @@ class VGG19_pytorch(nn.Module):
             raise NotImplementedError(
                 "VGG19_pytorch: only the input gradient is built (no weight gradients); freeze the parameters as train.py "
                 "does (`for p in vggnet.parameters(): p.requires_grad = False`)")
-        for k in out_keys:
-            if k not in arch.VGG_KEYS:
-                raise KeyError(k)
+        _check_vgg_keys(out_keys)
         if not out_keys:
             return []
         uniq = list(dict.fromkeys(out_keys))    # (a key requested twice: the same tensor twice, autograd adds its gradients)
         outs = _VGGInputGrad.apply(x, self, uniq, preprocess)
         return [outs[uniq.index(k)] for k in out_keys]
 
-    def _bwd_packs(self, name):
-        """kind -> packed input-gradient filters of a 3x3 layer (vgg_bwd_weight), in the module's cache under their own keys."""
-        w = getattr(self, name).weight
-        key = "vgg_bwd." + name
-
-        def get(kind):
-            if kind == "winograd":
-                return self._cache.get(key + ":wino", w, lambda w: ops.pack_winograd_weight(vgg_bwd_weight(w)))
-            if kind == "ws":
-                return self._cache.get(key + ":ws", w, lambda w: ops.pack_ws_weight(vgg_bwd_weight(w)))
-            return self._cache.get(key, w, lambda w: ops.pack_conv_weight(vgg_bwd_weight(w)))
-        return get
-
     def _input_grad(self, saved, g_ext, preprocess):
         """d x from the saved post-ReLU outputs R and the incoming gradients of the requested keys.  Layer by layer, deepest
         first: dZ = (dX + g(r)) * [R > 0] (ops.vgg_act_bwd), or through a pool (ops.vgg_pool_act_bwd), then the convolution's
         input gradient dX = conv3x3(dZ, W^T flipped) on the forward's engines; conv1_1's 3-channel one on ops.vgg_conv1_bwd."""
         keys = arch.VGG_KEYS
-        conv_names = {("r%s" % n[4:].replace("_", "")): n for n, _, _ in arch.VGG_CONVS}
         i = max((keys.index(k) for k in g_ext), default=-1)
         g = None                    # gradient w.r.t. the output of keys[i] from the layers behind it
         while i >= 0:
@@ -270,14 +299,14 @@ class VGG19_pytorch(nn.Module):
                 i, key = i - 1, rk
             else:
                 dZ = ops.vgg_act_bwd(g, g_ext.get(key), saved[key], out=g)
-            name = conv_names[key]
+            name = _VGG_CONV_OF[key]
             if name == "conv1_1":
                 w = self.conv1_1.weight
                 wt = self._cache.get("vgg_bwd.conv1_1" + (":pre" if preprocess else ""), w,
                                      lambda w: vgg_bwd_weight_conv1(w, preprocess))
                 return ops.vgg_conv1_bwd(dZ, wt)
-            wt = self._cache.get("vgg_bwd." + name + ":wt", getattr(self, name).weight, vgg_bwd_weight)
-            g = ops.conv3x3(dZ, wt, self._bwd_packs(name), None, layer="vgg_bwd." + name)
+            wt, packs = _bwd_filters(self._cache, "vgg_bwd." + name, getattr(self, name).weight, vgg_bwd_weight)
+            g = ops.conv3x3(dZ, wt, packs, None, layer="vgg_bwd." + name)
             del dZ
             i -= 1
         return None
@@ -287,13 +316,10 @@ class VGG19_pytorch(nn.Module):
         pool-fused layer too) — the backward's masks and routes."""
         x = x.detach().float() if _gray else x.detach().contiguous().float()
         N = x.shape[0]
-        for k in out_keys:
-            if k not in arch.VGG_KEYS:
-                raise KeyError(k)
+        _check_vgg_keys(out_keys)
         last = max(arch.VGG_KEYS.index(k) for k in out_keys) if out_keys else -1
         out = {}
         cur = x
-        conv_names = {("r%s" % n[4:].replace("_", "")): n for n, _, _ in arch.VGG_CONVS}
         pooled = None
         for i, key in enumerate(arch.VGG_KEYS):
             if i > last:
@@ -305,19 +331,19 @@ class VGG19_pytorch(nn.Module):
                     cur = ops.maxpool2x2(cur) if self._pool == "max" else ops.avgpool2x2(cur)
             elif (self._pool == "max" and ops.pool_fusion() and i + 1 <= last and arch.VGG_KEYS[i + 1][0] == "p"
                   and min(cur.shape[2:]) >= 2
-                  and ops.winograd_selected(N, cur.shape[1], cur.shape[2], cur.shape[3], getattr(self, conv_names[key]).weight.shape[0],
-                                            layer="vgg." + conv_names[key])):
+                  and ops.winograd_selected(N, cur.shape[1], cur.shape[2], cur.shape[3], getattr(self, _VGG_CONV_OF[key]).weight.shape[0],
+                                            layer="vgg." + _VGG_CONV_OF[key])):
                 # relu1_2 / relu2_2 / relu3_4 / relu4_4 -> pool: the pooled tensor comes out of the convolution's own launch; the
                 # full-resolution one only when somebody asked for it
-                conv = getattr(self, conv_names[key])
+                conv = getattr(self, _VGG_CONV_OF[key])
                 if ops.layer_record is not None:
-                    ops.layer_record.append(dict(layer="vgg." + conv_names[key], Cin=cur.shape[1], Cout=conv.weight.shape[0],
+                    ops.layer_record.append(dict(layer="vgg." + _VGG_CONV_OF[key], Cin=cur.shape[1], Cout=conv.weight.shape[0],
                                                  H=cur.shape[2], W=cur.shape[3], dil=1, in_up=1, in_sub=1, eligible=True))
-                cur, pooled = ops.conv2d_winograd_pool(cur, _packs(self._cache, conv_names[key], conv.weight)("winograd"),
+                cur, pooled = ops.conv2d_winograd_pool(cur, _packs(self._cache, _VGG_CONV_OF[key], conv.weight)("winograd"),
                                                        conv.bias.detach(), act=ops.ACT_RELU,
                                                        want_full=key in out_keys or saved is not None)
             else:
-                name = conv_names[key]
+                name = _VGG_CONV_OF[key]
                 conv = getattr(self, name)
                 bias = conv.bias.detach()
                 if name == "conv1_1" and preprocess:
@@ -358,14 +384,13 @@ class _WarpTrain(torch.autograd.Function):
         saved = {}
         theta, phi = module._trunk_forward_saving(trunkA.detach(), trunkB.detach(), saved)
         ctx.module, ctx.names = module, names
-        ctx.saved_keys = tuple(saved)
-        ctx.save_for_backward(*saved.values())
+        _save_dict(ctx, saved)
         return theta, phi
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g_theta, g_phi):
-        tensors = dict(zip(ctx.saved_keys, ctx.saved_tensors))
+        tensors = _saved_dict(ctx)
         need = {n for n, flag in zip(ctx.names, ctx.needs_input_grad[4:]) if flag}
         seam = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
         dA, dB, grads = ctx.module._trunk_backward(tensors, g_theta, g_phi, need, need_trunk_input_grad=seam)
@@ -582,9 +607,7 @@ class WarpNet(nn.Module):
         filled."""
         B_lab_map, A2, A3, A4, A5, B2, B3, B4, B5 = ins
         fh, fw = int(B_lab_map.shape[2] / 4), int(B_lab_map.shape[3] / 4)
-        for n, p in self._trunk_named_parameters():
-            if p.requires_grad and (not p.is_cuda or p.dtype != torch.float32):
-                raise RuntimeError(f"WarpNet: parameter {n} must be a float32 ROCm tensor for the training path")
+        _check_trainable(self._trunk_named_parameters(), "WarpNet")
         with torch.no_grad():
             trunkA = self._heads(A2, A3, A4, A5)
             trunkB = self._heads(B2, B3, B4, B5)
@@ -603,19 +626,6 @@ class WarpNet(nn.Module):
         theta, phi = _WarpTrain.apply(trunkA, trunkB, self, tuple(n for n, _ in named), *(p for _, p in named))
         y, sim, _ = fused_correlation(theta, phi, blab.view(N, 3, -1), float(temperature), fh, fw, WTA_scale_weight)
         return _Up4.apply(y), _Up4.apply(sim)
-
-    def _bwd_packs(self, key, conv):
-        """kind -> packed padded-input-gradient filters of a residual block's 3x3 layer (vgg_bwd_weight), under "warp_bwd." keys."""
-        w = conv.weight
-        ck = "warp_bwd." + key
-
-        def get(kind):
-            if kind == "winograd":
-                return self._cache.get(ck + ":wino", w, lambda w: ops.pack_winograd_weight(vgg_bwd_weight(w)))
-            if kind == "ws":
-                return self._cache.get(ck + ":ws", w, lambda w: ops.pack_ws_weight(vgg_bwd_weight(w)))
-            return self._cache.get(ck, w, lambda w: ops.pack_conv_weight(vgg_bwd_weight(w)))
-        return get
 
     def _trunk_forward_saving(self, trunkA, trunkB, saved):
         """Both sides as one batch of 2N images through the shared blocks, then theta on the A half and phi on the B half."""
@@ -637,12 +647,8 @@ class WarpNet(nn.Module):
         for which, g, sl in (("theta", g_theta, slice(0, N)), ("phi", g_phi, slice(N, M))):
             conv = getattr(self, which)
             dt = ops.warp_cn_bwd(t["t." + which], t["mean." + which], g.contiguous())
-            if which + ".weight" in need or which + ".bias" in need:
-                dW, db = ops.warp_k1_wgrad(dt, F[sl])
-                if which + ".weight" in need:
-                    grads[which + ".weight"] = dW
-                if which + ".bias" in need:
-                    grads[which + ".bias"] = db
+            if _wants(need, which):
+                _put_wb(grads, need, which, *ops.warp_k1_wgrad(dt, F[sl]))
             if need_blocks:
                 wt = self._cache.get("warp_bwd." + which, conv.weight,
                                      lambda w: ops.pack_conv_weight(w.detach().transpose(0, 1).contiguous()))
@@ -653,34 +659,26 @@ class WarpNet(nn.Module):
         for b in reversed(range(arch.WARP_NUM_RESBLOCKS)):
             blk = self.layer[b]
             a = blk.prelu.weight.detach()
-            pre = f"layer.{b}."
+            c1, c2 = f"layer.{b}.conv1", f"layer.{b}.conv2"
             sp = torch.empty((2, M * C), device=F.device, dtype=torch.float64)
             # second site: out = prelu(n2 + x)
             dz, du, _ = ops.warp_norm_prelu_bwd(g, t[f"n2.{b}"], t[f"rstd2.{b}"], a, skip=t[f"x{b}"], slope_part=sp[0])
-            if pre + "conv2.weight" in need or pre + "conv2.bias" in need:
-                dW, db = ops.cvn_wgrad(dz, ops.warp_reflect_pad(t[f"p1.{b}"]))
-                if pre + "conv2.weight" in need:
-                    grads[pre + "conv2.weight"] = dW
-                if pre + "conv2.bias" in need:
-                    grads[pre + "conv2.bias"] = db
-            wt = self._cache.get(f"warp_bwd.layer.{b}.conv2:wt", blk.conv2.weight, vgg_bwd_weight)
-            gp = ops.conv3x3(dz, wt, self._bwd_packs(f"layer.{b}.conv2", blk.conv2), None, layer=f"warp_bwd.layer.{b}.conv2")
+            if _wants(need, c2):
+                _put_wb(grads, need, c2, *ops.cvn_wgrad(dz, ops.warp_reflect_pad(t[f"p1.{b}"])))
+            wt, packs = _bwd_filters(self._cache, "warp_bwd." + c2, blk.conv2.weight, vgg_bwd_weight)
+            gp = ops.conv3x3(dz, wt, packs, None, layer="warp_bwd." + c2)
             g = ops.warp_fold(gp)
             del gp, dz
             # first site: p1 = prelu(n1)
             dz, _, _ = ops.warp_norm_prelu_bwd(g, t[f"n1.{b}"], t[f"rstd1.{b}"], a, slope_part=sp[1])
-            if pre + "conv1.weight" in need or pre + "conv1.bias" in need:
-                dW, db = ops.cvn_wgrad(dz, ops.warp_reflect_pad(t[f"x{b}"]))
-                if pre + "conv1.weight" in need:
-                    grads[pre + "conv1.weight"] = dW
-                if pre + "conv1.bias" in need:
-                    grads[pre + "conv1.bias"] = db
-            if pre + "prelu.weight" in need:
-                grads[pre + "prelu.weight"] = ops.warp_slope_sum(sp)
+            if _wants(need, c1):
+                _put_wb(grads, need, c1, *ops.cvn_wgrad(dz, ops.warp_reflect_pad(t[f"x{b}"])))
+            if f"layer.{b}.prelu.weight" in need:
+                grads[f"layer.{b}.prelu.weight"] = ops.warp_slope_sum(sp)
             if b == 0 and not need_trunk_input_grad:
                 return None, None, grads
-            wt = self._cache.get(f"warp_bwd.layer.{b}.conv1:wt", blk.conv1.weight, vgg_bwd_weight)
-            gp = ops.conv3x3(dz, wt, self._bwd_packs(f"layer.{b}.conv1", blk.conv1), None, layer=f"warp_bwd.layer.{b}.conv1")
+            wt, packs = _bwd_filters(self._cache, "warp_bwd." + c1, blk.conv1.weight, vgg_bwd_weight)
+            gp = ops.conv3x3(dz, wt, packs, None, layer="warp_bwd." + c1)
             g = ops.warp_fold(gp, skip=du)
             del gp, dz, du
         return g[:N], g[N:], grads
@@ -808,15 +806,15 @@ class _CVNTrain(torch.autograd.Function):
         saved, rstd = {}, {}
         ab = module._forward(x, saved=saved, rstd=rstd)
         saved["ab"] = ab
+        saved.update(("rstd:" + k, v) for k, v in rstd.items())
         ctx.module, ctx.names = module, names
-        ctx.saved_keys = tuple(saved) + tuple("rstd:" + k for k in rstd)
-        ctx.save_for_backward(*saved.values(), *rstd.values())
+        _save_dict(ctx, saved)
         return ab
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g_ab):
-        tensors = dict(zip(ctx.saved_keys, ctx.saved_tensors))
+        tensors = _saved_dict(ctx)
         need = {n for n, flag in zip(ctx.names, ctx.needs_input_grad[3:]) if flag}
         dx, grads = ctx.module._backward(tensors, g_ab.contiguous(), need, ctx.needs_input_grad[0])
         return (dx, None, None) + tuple(grads.get(n) for n in ctx.names)
@@ -938,24 +936,13 @@ class ColorVidNet(nn.Module):
             _check_input(x, "ColorVidNet")
         if x.dtype != torch.float32:
             raise TypeError(f"ColorVidNet: the training path takes a float32 input (got {x.dtype})")
-        named = [(n, p) for n, p in self.named_parameters()]
-        for n, p in named:
-            if p.requires_grad and (not p.is_cuda or p.dtype != torch.float32):
-                raise RuntimeError(f"ColorVidNet: parameter {n} must be a float32 ROCm tensor for the training path")
+        named = list(self.named_parameters())
+        _check_trainable(named, "ColorVidNet")
         return _CVNTrain.apply(x, self, tuple(n for n, _ in named), *(p for _, p in named))
 
-    def _bwd_packs(self, key, pad_to=None):
-        """kind -> packed input-gradient filters of a 3x3 layer (cvn_bwd_weight), in the module's cache under their own keys."""
-        w = self._mod(key).weight
-        ck = "cvn_bwd." + key
-
-        def get(kind):
-            if kind == "winograd":
-                return self._cache.get(ck + ":wino", w, lambda w: ops.pack_winograd_weight(cvn_bwd_weight(w, pad_to)))
-            if kind == "ws":
-                return self._cache.get(ck + ":ws", w, lambda w: ops.pack_ws_weight(cvn_bwd_weight(w, pad_to)))
-            return self._cache.get(ck, w, lambda w: ops.pack_conv_weight(cvn_bwd_weight(w, pad_to)))
-        return get
+    def _bwd_filters(self, key, pad_to=None):
+        """(filters, packs) of the input gradient of the 3x3 layer `key` (cvn_bwd_weight), under "cvn_bwd." keys."""
+        return _bwd_filters(self._cache, "cvn_bwd." + key, self._mod(key).weight, lambda w: cvn_bwd_weight(w, pad_to))
 
     def _backward(self, t, g_ab, need, need_dx):
         """Parameter gradients (names in `need`) and d x (need_dx) from the saved tensors `t` (ColorVidNet._forward(saved=...)):
@@ -964,11 +951,7 @@ class ColorVidNet(nn.Module):
         with W^T flipped (ops.conv3x3)."""
         grads = {}
         dZ, dW, db = ops.cvn_head_bwd(t["ab"], g_ab, self._out_weight(), t["c10_2"], slope=0.2)
-        k_ab = arch.CVN_OUT["key"]
-        if k_ab + ".weight" in need:
-            grads[k_ab + ".weight"] = dW
-        if k_ab + ".bias" in need:
-            grads[k_ab + ".bias"] = db
+        _put_wb(grads, need, arch.CVN_OUT["key"], dW, db)
         dZ_of = {"c10_2": dZ}
         adder = {c["add"]: c["dst"] for c in arch.CVN_CONVS if c["add"] is not None}    # skip output -> the block it adds into
         contrib = {}                                                                        # activation -> {kind: gradient}
@@ -992,22 +975,16 @@ class ColorVidNet(nn.Module):
                 dZ_of[dst] = dZ
             X = t[src] if pre is None else t["nss:" + src] if pre == "norm_ss" else t["n:" + src]
             in_up = 2 if pre == "up" else 1
-            if key + ".weight" in need or key + ".bias" in need:
-                dW, db = ops.cvn_wgrad(dZ, X, dil=c["dil"], in_up=in_up)
-                if key + ".weight" in need:
-                    grads[key + ".weight"] = dW
-                if key + ".bias" in need:
-                    grads[key + ".bias"] = db
-            w = self._mod(key).weight
+            if _wants(need, key):
+                _put_wb(grads, need, key, *ops.cvn_wgrad(dZ, X, dil=c["dil"], in_up=in_up))
             if src == "x":
                 if need_dx:
-                    cin = w.shape[1]
-                    pad_to = max(32, -(-cin // 32) * 32)
-                    wt = self._cache.get("cvn_bwd." + key + ":wt", w, lambda w: cvn_bwd_weight(w, pad_to))
-                    dx = ops.conv3x3(dZ, wt, self._bwd_packs(key, pad_to), None, dil=c["dil"], layer="cvn_bwd." + key)[:, :cin]
+                    cin = self._mod(key).weight.shape[1]
+                    wt, packs = self._bwd_filters(key, pad_to=max(32, -(-cin // 32) * 32))
+                    dx = ops.conv3x3(dZ, wt, packs, None, dil=c["dil"], layer="cvn_bwd." + key)[:, :cin]
                 continue
-            wt = self._cache.get("cvn_bwd." + key + ":wt", w, cvn_bwd_weight)
-            gi = ops.conv3x3(dZ, wt, self._bwd_packs(key), None, dil=c["dil"], layer="cvn_bwd." + key)
+            wt, packs = self._bwd_filters(key)
+            gi = ops.conv3x3(dZ, wt, packs, None, dil=c["dil"], layer="cvn_bwd." + key)
             kind = {None: "raw", "norm": "full", "norm_ss": "ss", "up": "up"}[pre]
             assert kind not in contrib.get(src, {}), (src, kind)
             contrib.setdefault(src, {})[kind] = gi

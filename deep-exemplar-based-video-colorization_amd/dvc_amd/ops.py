@@ -1082,6 +1082,16 @@ def vgg_conv1_bwd(dZ, w_t):
 
 
 # ---- ColorVidNet backward (csrc/cvn_bwd.hip; dvc_amd/nets.py walks the layers)
+def _slotted_wgrad(name, launch, S, Cout, Cin, k, device):
+    """The workspace protocol of the two weight-gradient entry points: S partial slots of ld = Cout*Cin*k*k + Cout floats and an
+    `out` of ld floats; launch(part, out) -> rc.  Returns out split into (dW [Cout,Cin,k,k], db [Cout])."""
+    nw = Cout * Cin * k * k
+    part = torch.empty(S * (nw + Cout), device=device, dtype=torch.float32)
+    out = torch.empty(nw + Cout, device=device, dtype=torch.float32)
+    _lib.check(launch(part, out), name)
+    return out[:nw].view(Cout, Cin, k, k), out[nw:]
+
+
 def cvn_wgrad_splits(N, Cin, Cout, H, W):
     """The default number of position slots dvc_cvn_wgrad splits a layer's sum over."""
     return int(_lib.load().dvc_cvn_wgrad_splits(N, Cin, Cout, H, W))
@@ -1097,12 +1107,8 @@ def cvn_wgrad(dZ, X, *, dil=1, in_up=1, splits=None):
     Cin = X.shape[1]
     assert X.shape[0] == N and tuple(X.shape[2:]) == (H // in_up, W // in_up), (X.shape, dZ.shape, in_up)
     S = cvn_wgrad_splits(N, Cin, Cout, H, W) if splits is None else int(splits)
-    ld = Cout * Cin * 9 + Cout
-    part = torch.empty(S * ld, device=dZ.device, dtype=torch.float32)
-    out = torch.empty(ld, device=dZ.device, dtype=torch.float32)
-    _lib.check(lib.dvc_cvn_wgrad(_p(dZ), _p(X), N, Cin, Cout, H, W, dil, in_up, S, _p(part), part.numel(), _p(out), _stream()),
-               "dvc_cvn_wgrad")
-    return out[:Cout * Cin * 9].view(Cout, Cin, 3, 3), out[Cout * Cin * 9:]
+    return _slotted_wgrad("dvc_cvn_wgrad", lambda part, out: lib.dvc_cvn_wgrad(
+        _p(dZ), _p(X), N, Cin, Cout, H, W, dil, in_up, S, _p(part), part.numel(), _p(out), _stream()), S, Cout, Cin, 3, dZ.device)
 
 
 def cvn_head_bwd(ab, grad_ab, w_ab, R, slope=0.2):
@@ -1209,12 +1215,8 @@ def warp_k1_wgrad(dT, F, *, splits=None):
     P = dT[0, 0].numel()
     assert F.shape[0] == N and F[0, 0].numel() == P, (dT.shape, F.shape)
     S = warp_k1_wgrad_splits(N, Cin, Cout, P) if splits is None else int(splits)
-    ld = Cout * Cin + Cout
-    part = torch.empty(S * ld, device=dT.device, dtype=torch.float32)
-    out = torch.empty(ld, device=dT.device, dtype=torch.float32)
-    _lib.check(lib.dvc_warp_k1_wgrad(_p(dT), _p(F), N, Cin, Cout, P, S, _p(part), part.numel(), _p(out), _stream()),
-               "dvc_warp_k1_wgrad")
-    return out[:Cout * Cin].view(Cout, Cin, 1, 1), out[Cout * Cin:]
+    return _slotted_wgrad("dvc_warp_k1_wgrad", lambda part, out: lib.dvc_warp_k1_wgrad(
+        _p(dT), _p(F), N, Cin, Cout, P, S, _p(part), part.numel(), _p(out), _stream()), S, Cout, Cin, 1, dT.device)
 
 
 def warp_norm_prelu_bwd(g, n, rstd, slope_t, skip=None, slope_part=None):

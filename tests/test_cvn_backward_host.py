@@ -12,22 +12,12 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from cabi_common import _fails, _lib
 from bwd_audit import ref_inorm_bwd as _inorm_bwd64      # (the float64 restatement of dvc_cvn_inorm_bwd; the audit uses it too)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ONE = ctypes.c_void_p(256)      # a non-null address that is never dereferenced: every call below fails validation first
 NEW = ["dvc_cvn_wgrad_splits", "dvc_cvn_wgrad", "dvc_cvn_head_bwd_workspace_floats", "dvc_cvn_head_bwd", "dvc_cvn_inorm_bwd"]
-
-
-def _lib():
-    from dvc_amd import _lib
-    return _lib.load()
-
-
-def _fails(rc, lib, needle):
-    assert rc != 0, "accepted"
-    msg = lib.dvc_last_error()
-    assert needle.encode() in msg, msg
 
 
 def test_new_entry_points_in_header_table_and_exports():

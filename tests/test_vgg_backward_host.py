@@ -6,20 +6,10 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from cabi_common import _fails, _lib
 from oracle import dvc_oracle as O
 
 ONE = ctypes.c_void_p(256)      # a non-null address that is never dereferenced: every call below fails validation first
-
-
-def _lib():
-    from dvc_amd import _lib
-    return _lib.load()
-
-
-def _fails(rc, lib, needle):
-    assert rc != 0, "accepted"
-    msg = lib.dvc_last_error()
-    assert needle.encode() in msg, msg
 
 
 def test_act_bwd_validation_without_gpu():

@@ -13,6 +13,7 @@ import torch.nn.functional as F
 
 import warp_bwd_reference as R
 from bwd_audit import relerr
+from cabi_common import _fails, _lib
 from oracle import dvc_oracle as O
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -23,17 +24,6 @@ NEW = ["dvc_warp_up4_bwd", "dvc_warp_prelu_fwd", "dvc_warp_cn_bwd", "dvc_warp_k1
 BOUND = 1e-12
 TRUNK_NAMES = [f"layer.{b}.{k}" for b in range(3) for k in ("conv1.weight", "conv1.bias", "conv2.weight", "conv2.bias",
                                                              "prelu.weight")] + ["theta.weight", "theta.bias", "phi.weight", "phi.bias"]
-
-
-def _lib():
-    from dvc_amd import _lib
-    return _lib.load()
-
-
-def _fails(rc, lib, needle):
-    assert rc != 0, "accepted"
-    msg = lib.dvc_last_error()
-    assert needle.encode() in msg, msg
 
 
 def _block_sd(seed, ch=6, a=0.25):

@@ -13,9 +13,9 @@ with the weight-gradient kernel's share of the fp32 MFMA peak per layer class.
     python tools/cvn_bwd_probe.py --hip-only   # 1 warm-up + 5 training steps at B = 1 (for a rocprofv3 --kernel-trace --stats run)
 """
 import contextlib
+import functools
 import io
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -25,43 +25,13 @@ import torch  # noqa: E402
 
 from dvc_amd import arch, ops, synth  # noqa: E402
 from models.ColorVidNet import ColorVidNet  # noqa: E402
+import probe_timing  # noqa: E402
+from probe_timing import peak_mem  # noqa: E402
 
 PEAK = 157.3e12     # fp32 MFMA, MI355X
 H, W = 216, 384
 dev = torch.device("cuda")
-_filler = None
-
-
-def device_time(fn, reps):
-    """ms per call with the launch queue primed (filler GEMMs enqueued first: the events bracket kernel execution only)."""
-    global _filler
-    if _filler is None:
-        _filler = (torch.randn(8192, 8192, device=dev), torch.randn(8192, 8192, device=dev), torch.empty(8192, 8192, device=dev))
-    fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    for _ in range(2 + 4 * reps):
-        torch.mm(_filler[0], _filler[1], out=_filler[2])
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / reps
-
-
-def median_time(fn, reps, rounds=3):
-    return statistics.median(device_time(fn, reps) for _ in range(rounds))
-
-
-def peak_mem(fn):
-    torch.cuda.synchronize()
-    base = torch.cuda.memory_allocated()
-    torch.cuda.reset_peak_memory_stats()
-    keep = fn()
-    torch.cuda.synchronize()
-    del keep
-    return (torch.cuda.max_memory_allocated() - base) / 2**20
+median_time = functools.partial(probe_timing.median_time, rounds=3)
 
 
 def layer_shapes(B):
@@ -139,9 +109,8 @@ def main():
             a[2] += 2.0 * B * h * w * ci * co * 9
             if c["src"] != "x":
                 key = c["key"]
-                wt = m._cache.get("cvn_bwd." + key + ":wt", m._mod(key).weight, lambda w_: w_.detach().transpose(0, 1).flip(2, 3)
-                                  .contiguous())
-                ti += median_time(lambda: ops.conv3x3(dZ, wt, m._bwd_packs(key), None, dil=c["dil"], layer="cvn_bwd." + key), 5)
+                wt, packs = m._bwd_filters(key)
+                ti += median_time(lambda: ops.conv3x3(dZ, wt, packs, None, dil=c["dil"], layer="cvn_bwd." + key), 5)
         print(f"  backward parts (each layer alone): weight gradients {tw:.3f} ms, input gradients {ti:.3f} ms, "
               f"rest (head, InstanceNorm, ReLU, d x of conv1_1.0) ~{max(t_b - tw - ti, 0):.3f} ms")
         for cls, (n, tl, f) in classes.items():

@@ -14,9 +14,9 @@ then the torch composition on the device (oracle.vgg19_forward under autograd, v
     python tools/vgg_bwd_probe.py --hip-only   # only this library's forward + backward (for a rocprofv3 --kernel-trace --stats run)
 """
 import contextlib
+import functools
 import io
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -27,6 +27,8 @@ import torch  # noqa: E402
 from dvc_amd import arch, ops, synth  # noqa: E402
 from models.NonlocalNet import VGG19_pytorch  # noqa: E402
 from oracle import dvc_oracle as O  # noqa: E402
+import probe_timing  # noqa: E402
+from probe_timing import peak_mem  # noqa: E402
 from utils.util import tensor_lab2rgb  # noqa: E402
 
 PEAK = 157.3e12     # fp32 MFMA, MI355X
@@ -35,39 +37,7 @@ B, H, W = 16, 216, 384
 KEYS = ["r12", "r22", "r32", "r42", "r52"]
 ITERS = 10
 dev = torch.device("cuda")
-_filler = None
-
-
-def device_time(fn, reps):
-    """ms per call with the launch queue primed (filler GEMMs enqueued first: the events bracket kernel execution only)."""
-    global _filler
-    if _filler is None:
-        _filler = (torch.randn(8192, 8192, device=dev), torch.randn(8192, 8192, device=dev), torch.empty(8192, 8192, device=dev))
-    fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    for _ in range(2 + 4 * reps):
-        torch.mm(_filler[0], _filler[1], out=_filler[2])
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / reps
-
-
-def median_time(fn, reps, rounds=5):
-    return statistics.median(device_time(fn, reps) for _ in range(rounds))
-
-
-def peak_mem(fn):
-    torch.cuda.synchronize()
-    base = torch.cuda.memory_allocated()
-    torch.cuda.reset_peak_memory_stats()
-    keep = fn()
-    torch.cuda.synchronize()
-    del keep
-    return (torch.cuda.max_memory_allocated() - base) / 2**20
+median_time = functools.partial(probe_timing.median_time, rounds=5)
 
 
 def conv_flops(keys):

@@ -14,6 +14,7 @@ forward + backward), timed in the same call, alternating with the HIP path.
     python tools/warp_bwd_probe.py              # the table
     python tools/warp_bwd_probe.py --hip-only   # 1 warm-up + 5 training steps at N = 1 (for a rocprofv3 --kernel-trace --stats run)
 """
+import functools
 import os
 import statistics
 import sys
@@ -27,32 +28,13 @@ import torch.nn.functional as F  # noqa: E402
 from dvc_amd import ops, synth  # noqa: E402
 from models.NonlocalNet import WarpNet  # noqa: E402
 from oracle import dvc_oracle as O  # noqa: E402
+import probe_timing  # noqa: E402
+from probe_timing import peak_mem, spread  # noqa: E402
 
 PEAK = 157.3e12     # fp32 MFMA, MI355X
 h, w, T = 54, 96, 0.01
 dev = torch.device("cuda")
-_filler = None
-
-
-def device_time(fn, reps):
-    """ms per call with the launch queue primed (filler GEMMs enqueued first: the events bracket kernel execution only)."""
-    global _filler
-    if _filler is None:
-        _filler = (torch.randn(8192, 8192, device=dev), torch.randn(8192, 8192, device=dev), torch.empty(8192, 8192, device=dev))
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    for _ in range(2 + 4 * reps):
-        torch.mm(_filler[0], _filler[1], out=_filler[2])
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / reps
-
-
-def spread(samples):
-    s = sorted(samples)
-    return s[max(0, int(0.1 * (len(s) - 1)))], statistics.median(s), s[min(len(s) - 1, int(round(0.9 * (len(s) - 1))))]
+device_time = functools.partial(probe_timing.device_time, warm=False)     # (run() warms every shape itself)
 
 
 def fmt(name, samples):
@@ -144,12 +126,7 @@ def run(N, rounds=7):
     print(fmt("dvc_warp_k1_wgrad 256x256, K = N*P", k1) + f"   {flops / (statistics.median(k1) * 1e-3) / PEAK:.3f} of the fp32 MFMA peak")
     # peak memory on top of what is live before the call
     for name, fn in (("saving forward + backward", hip_step), ("torch composition", comp_step)):
-        torch.cuda.synchronize()
-        base = torch.cuda.memory_allocated()
-        torch.cuda.reset_peak_memory_stats()
-        fn()
-        torch.cuda.synchronize()
-        print(f"  peak memory, {name:32s} {(torch.cuda.max_memory_allocated() - base) / 2 ** 20:9.1f} MiB")
+        print(f"  peak memory, {name:32s} {peak_mem(fn):9.1f} MiB")
 
 
 if __name__ == "__main__":
