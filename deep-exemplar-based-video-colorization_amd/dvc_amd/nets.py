@@ -337,8 +337,7 @@ class VGG19_pytorch(nn.Module):
                 # full-resolution one only when somebody asked for it
                 conv = getattr(self, _VGG_CONV_OF[key])
                 if ops.layer_record is not None:
-                    ops.layer_record.append(dict(layer="vgg." + _VGG_CONV_OF[key], Cin=cur.shape[1], Cout=conv.weight.shape[0],
-                                                 H=cur.shape[2], W=cur.shape[3], dil=1, in_up=1, in_sub=1, eligible=True))
+                    ops.record_layer("vgg." + _VGG_CONV_OF[key], cur.shape[1], conv.weight.shape[0], cur.shape[2], cur.shape[3])
                 cur, pooled = ops.conv2d_winograd_pool(cur, _packs(self._cache, _VGG_CONV_OF[key], conv.weight)("winograd"),
                                                        conv.bias.detach(), act=ops.ACT_RELU,
                                                        want_full=key in out_keys or saved is not None)
@@ -1057,9 +1056,8 @@ class ColorVidNet(nn.Module):
                     u, b = self._dual_pack(c, e)
                     if ops.layer_record is not None:
                         for cc_, src_ in ((c, srcA), (e, srcB)):
-                            ops.layer_record.append(dict(layer="cvn." + cc_["key"], Cin=src_.shape[1], Cout=cc_["cout"], H=src_.shape[2],
-                                                         W=src_.shape[3], dil=cc_["dil"], in_up=2 if cc_["pre"] == "up" else 1, in_sub=1,
-                                                         eligible=True, dual=c["key"]))
+                            ops.record_layer("cvn." + cc_["key"], src_.shape[1], cc_["cout"], src_.shape[2], src_.shape[3], dil=cc_["dil"],
+                                             in_up=2 if cc_["pre"] == "up" else 1, dual=c["key"])
                     acts[c["dst"]] = ops.conv2d_winograd_dual(srcA, srcB, u, b, dil=c["dil"], in_upA=2 if c["pre"] == "up" else 1,
                                                               act=act_map[c["act"]], act_slope=0.2)
                     if c["dst"] in norm_uses:

@@ -390,3 +390,158 @@ def test_training_side_gemm_guard_refuses_reduced_precision_and_cpu_tensors():
     with pytest.raises(RuntimeError, match="ROCm tensor"):
         ops.bmm(torch.zeros(1, 2, 2), torch.zeros(1, 2, 2))
     assert ops.gemm_lib() in (True, False)
+
+
+# ---- the switch registry of dvc_amd/ops.py.  Getter value for the variable unset, "0", "1" and "yes", recorded from the commit
+# before the registry (93d8697), where every switch parsed its variable by hand: `== "1"` for some, `!= "0"` for the others.
+_DL = ["cvn.conv1_1.2", "cvn.conv1_2", "cvn.conv2_1", "cvn.conv2_2", "cvn.conv3_1", "cvn.conv3_2"]
+ENV_PARSE = {
+    # variable:            (getter,              unset,  "0",    "1",   "yes")
+    "DVC_AUTOTUNE":        ("autotune_enabled",   False,  False,  True,  False),
+    "DVC_WS_CONV":         ("ws_conv_enabled",    True,   False,  True,  True),
+    "DVC_POOL_FUSION":     ("pool_fusion",        True,   False,  True,  True),
+    "DVC_DUAL_CONV":       ("dual_conv_enabled",  True,   False,  True,  False),
+    "DVC_FUSE_REDUCE":     ("fuse_reduce",        True,   False,  True,  False),
+    "DVC_CONV_ALGO":       ("conv_algo",          "auto", "0",    "1",   "yes"),
+    "DVC_EXEMPLAR_MEMO":   ("exemplar_memo_mode", "on",   "off",  "on",  "on"),
+    "DVC_GEMM_LIB":        ("gemm_lib",           True,   False,  True,  True),
+    "DVC_GRAY_FUSION":     ("gray_fusion",        True,   False,  True,  True),
+    "DVC_GROUP_HEADS":     ("group_heads",        True,   False,  True,  True),
+    "DVC_FOLD_MERGE":      ("fold_merge",         True,   False,  True,  False),
+    "DVC_DIRECT_LAYERS":   ("direct_layers",      _DL,    ["0"],  ["1"], ["yes"]),
+}
+
+
+def test_switch_registry_parses_each_variable_as_before():
+    """A fresh interpreter per setting (the variables are read at import), every variable of the registry set to the same string:
+    each getter reports what the hand-written parse of the parent commit reported.  Importing ops loads no library."""
+    import json
+    import subprocess
+    import sys
+    from dvc_amd import ops
+    envs = {sw.env: sw.getter for sw in ops._SWITCHES if sw.env}
+    assert envs == {k: v[0] for k, v in ENV_PARSE.items()}                   # every entry of the registry is covered, by its getter
+    code = ("import json, sys; from dvc_amd import ops, _lib; assert _lib._lib is None; "
+            "v = {g: getattr(ops, g)() for g in sys.argv[1:]}; v['direct_layers'] = sorted(v['direct_layers']); print(json.dumps(v))")
+    pkg = os.path.join(ROOT, "deep-exemplar-based-video-colorization_amd")
+    for col, value in enumerate((None, "0", "1", "yes")):
+        env = {k: v for k, v in os.environ.items() if k not in ENV_PARSE}
+        env["PYTHONPATH"] = pkg + os.pathsep + env.get("PYTHONPATH", "")
+        if value is not None:
+            env.update({k: value for k in ENV_PARSE})
+        out = subprocess.run([sys.executable, "-c", code] + list(envs.values()), env=env, capture_output=True, text=True)
+        assert out.returncode == 0, out.stderr
+        got = json.loads(out.stdout)
+        for var, row in ENV_PARSE.items():
+            assert got[row[0]] == row[1 + col], (var, value, got[row[0]], row[1 + col])
+
+
+def test_graph_epoch_follows_every_launch_deciding_switch():
+    """graph._epoch() is nets.pack_epoch() plus the registry's launch-deciding entries: flipping each of them through its public
+    setter changes the tuple and restoring it restores the tuple; gemm_lib and exemplar_memo (not launch-deciding) do not."""
+    from dvc_amd import graph, ops
+    flips = {
+        "autotune_enabled": (lambda: ops.set_autotune(not ops.autotune_enabled()),) * 2,
+        "ws_conv_enabled": (lambda: ops.set_ws_conv(not ops.ws_conv_enabled()),) * 2,
+        "pool_fusion": (lambda: ops.set_pool_fusion(not ops.pool_fusion()),) * 2,
+        "dual_conv_enabled": (lambda: ops.set_dual_conv(not ops.dual_conv_enabled()),) * 2,
+        "fuse_reduce": (lambda: ops.set_fuse_reduce(not ops.fuse_reduce()),) * 2,
+        "conv_algo": (lambda: ops.set_conv_algo("direct"), lambda old=ops.conv_algo(): ops.set_conv_algo(old)),
+        "gray_fusion": (lambda: ops.set_gray_fusion(not ops.gray_fusion()),) * 2,
+        "group_heads": (lambda: ops.set_group_heads(not ops.group_heads()),) * 2,
+        "fold_merge": (lambda: ops.set_fold_merge(not ops.fold_merge()),) * 2,
+        "direct_layers": (lambda: ops.set_direct_layers(["vgg.conv3_1"]), lambda old=ops._direct_layers: ops.set_direct_layers(old)),
+    }
+    launch = [sw.getter for sw in ops._SWITCHES if sw.launch]
+    assert sorted(launch) == sorted(list(flips) + ["batch_plan_enabled"])
+    assert sorted(sw.getter for sw in ops._SWITCHES if not sw.launch) == ["exemplar_memo_mode", "gemm_lib"]
+    base = graph._epoch()
+    assert len(base) == 1 + len(launch)
+    for name, (flip, restore) in flips.items():
+        flip()
+        try:
+            assert graph._epoch() != base, name
+        finally:
+            restore()
+        assert graph._epoch() == base, name
+    with ops.batch_plan(not ops.batch_plan_enabled()):
+        assert graph._epoch() != base
+    assert graph._epoch() == base
+    old_gemm, old_memo = ops.gemm_lib(), ops.exemplar_memo_mode()
+    try:
+        ops.set_gemm_lib(not old_gemm)
+        ops.set_exemplar_memo(old_memo == "off")
+        assert graph._epoch() == base
+    finally:
+        ops.set_gemm_lib(old_gemm)
+        ops.set_exemplar_memo("verify" if old_memo == "verify" else old_memo == "on")
+    assert (ops.gemm_lib(), ops.exemplar_memo_mode()) == (old_gemm, old_memo)
+
+
+# what the five convolution wrappers (and the grouped launch) appended to ops.conv_record at 93d8697 for the calls below
+_R = dict(ksize=3, stride=1, dil=1, pad=1, pad_mode=0, in_up=1, in_sub=1, affine=False, in_prelu=False, residual=False)
+CONV_RECORDS = [
+    dict(N=2, Cin=8, H=27, W=45, Cout=16, ksize=3, stride=2, dil=1, pad=1, pad_mode=1, in_up=1, in_sub=1, affine=True, in_prelu=True,
+         residual=False, act=1),                                                                          # conv2d: no `algo`
+    dict(N=1, Cin=16, H=12, W=20, Cout=8, ksize=1, stride=1, dil=1, pad=0, pad_mode=0, in_up=1, in_sub=1, affine=False,
+         in_prelu=False, residual=True, act=0),
+    dict(_R, N=2, Cin=64, H=24, W=40, Cout=128, act=3, algo="direct-ws"),                                 # conv2d_ws
+    dict(_R, N=2, Cin=64, H=13, W=24, Cout=128, dil=2, pad=2, pad_mode=1, in_up=2, residual=True, act=2, algo="winograd"),
+    dict(_R, N=1, Cin=64, H=24, W=40, Cout=64, act=1, algo="winograd"),                                   # conv2d_winograd_pool
+    dict(_R, N=2, Cin=192, H=24, W=40, Cout=64, act=3, algo="winograd-dual"),              # virtual size, summed input channels
+    dict(_R, N=1, Cin=64, H=54, W=96, Cout=64, act=0, algo="winograd"),                                   # conv3x3_group, item 0
+    dict(_R, N=1, Cin=64, H=27, W=48, Cout=64, pad_mode=1, in_up=2, act=0, algo="winograd"),              # conv3x3_group, item 1
+]
+LAYER_RECORDS = [
+    dict(layer="warp.layer2_1.3", Cin=64, Cout=64, H=54, W=96, dil=1, in_up=1, in_sub=1, eligible=True),
+    dict(layer=None, Cin=64, Cout=64, H=27, W=48, dil=1, in_up=2, in_sub=1, eligible=True),
+    dict(layer="x.y", Cin=8, Cout=16, H=20, W=30, dil=1, in_up=1, in_sub=1, eligible=False),
+]
+
+
+def test_conv_and_layer_records_are_what_they_were(monkeypatch):
+    """ops._record_conv / ops.record_layer, directly and through the wrappers' call sites (CPU tensors, a library stand-in that
+    launches nothing): key for key and value for value the dicts the parent commit wrote out by hand —
+    including the general engine's missing `algo` and the dual launch's virtual size."""
+    from dvc_amd import _lib, ops
+
+    d = ops._conv_desc(2, 64, 13, 24, 128, dil=2, pad_mode=ops.PAD_REFLECT, in_up=2, act=ops.ACT_PRELU)
+    r = ops._record_conv(d, affine=False, in_prelu=False, residual=True, algo="winograd")
+    assert r == CONV_RECORDS[3]
+    d = ops._conv_desc(2, 8, 27, 45, 16, stride=2, pad=1, pad_mode=ops.PAD_REFLECT, act=ops.ACT_RELU, in_prelu=True)
+    r = ops._record_conv(d, affine=True, in_prelu=True, residual=False)
+    assert r == CONV_RECORDS[0] and "algo" not in r
+    assert (d.in_prelu, d.cfg, d.split_k, d.x_batch_stride, d.y_batch_stride, d.res_batch_stride, d.flags, d.w_batch_stride) == \
+        (1, -1, 0, 0, 0, 0, 0, 0)
+
+    class Stub:
+        def __getattr__(self, name):
+            def call(*args):
+                if name == "dvc_conv2d_winograd_split":
+                    args[2]._obj.value, args[3]._obj.value = 2, 99
+                return 0
+            return call
+
+    monkeypatch.setattr(_lib, "_lib", Stub())
+    monkeypatch.setattr(ops, "_need", lambda t, name: None)
+    monkeypatch.setattr(ops, "_stream", lambda: None)
+    monkeypatch.setattr(ops, "_stream_handle", lambda: 0)
+    monkeypatch.setattr(ops, "_ws_cache", {})
+    monkeypatch.setattr(ops, "conv_record", [])
+    monkeypatch.setattr(ops, "layer_record", [])
+    T = torch.zeros
+    ops.conv2d(T(2, 8, 27, 45), T(8, 9, 16), None, stride=2, pad=1, pad_mode=ops.PAD_REFLECT, act=ops.ACT_RELU, in_scale=T(16),
+               in_shift=T(16), in_slope_t=T(1))
+    ops.conv2d(T(1, 16, 12, 20), T(16, 1, 8), None, ksize=1, pad=0, residual=T(1, 8, 12, 20))
+    ops.conv2d_ws(T(2, 64, 24, 40), T(128 * 64 * 9), None, 128, act=ops.ACT_LEAKY, act_slope=0.2)
+    ops.conv2d_winograd(T(2, 64, 13, 24), T(4, 64, 4, 32, 4), None, dil=2, pad_mode=ops.PAD_REFLECT, in_up=2, act=ops.ACT_PRELU,
+                        residual=T(2, 128, 26, 48))
+    ops.conv2d_winograd_pool(T(1, 64, 24, 40), T(2, 64, 4, 32, 4), None, act=ops.ACT_RELU)
+    ops.conv2d_winograd_dual(T(2, 128, 12, 20), T(2, 64, 24, 40), T(2, 192, 4, 32, 4), None, in_upA=2, act=ops.ACT_LEAKY, act_slope=0.2)
+    w, u = T(64, 64, 3, 3), T(2, 64, 4, 32, 4)
+    ops.conv3x3_group([dict(x=T(1, 64, 54, 96), weight=w, packs=lambda kind: u, bias=None, defer_reduce=True, layer="warp.layer2_1.3"),
+                       dict(x=T(1, 64, 27, 48), weight=w, packs=lambda kind: u, bias=None, in_up=2, pad_mode=ops.PAD_REFLECT)])
+    assert ops.conv_record == CONV_RECORDS
+    ops.conv3x3(T(1, 8, 20, 30), T(16, 8, 3, 3), lambda kind: T(8, 9, 16), None, layer="x.y")
+    assert ops.layer_record == LAYER_RECORDS
+    assert "algo" not in ops.conv_record[-1]                        # (the 8 -> 16 layer went to the general engine)

@@ -1073,6 +1073,9 @@ def test_corr_merge_folded_into_pack_color_input(ops, h, w, B, T):
     odd.copy_(IA)
     assert odd.data_ptr() % 16 != 0
     assert torch.equal(ops.pack_color_input(odd, part, None, last), want)
+    # ... and the copy outlives the allocation of the warped Lab, a tensor of the copy's size made between the copy and the launches
+    got_o, warped_o = ops.pack_color_input(odd, part, None, last, want_warped=True)
+    assert torch.equal(got_o, want) and torch.equal(warped_o, ref["y_up"])
     # WTA / taps keep the materialised path
     assert isinstance(ops.corr_fwd(th, ph, bl, T, h, w, wta_scale=0.5, defer_merge=True), dict)
     assert isinstance(ops.corr_fwd(th, ph, bl, T, h, w, want_argmax=True, defer_merge=True), dict)
