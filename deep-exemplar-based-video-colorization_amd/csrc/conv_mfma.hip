@@ -691,6 +691,15 @@ static int wino_reduce(const DvcConvDesc* d, const ConvWinoArgs& s, int NB, int 
     return 0;
 }
 
+// A two-input launch may leave out the exactly-zero transform positions of its first input (UPZ, conv_wino_kernel.h) when patch
+// rows / columns 1 and 2 of every stored tile are the same element: nearest x2 upsampling read in place, dilation 1 (tile origins
+// even), pad 1, stride 1, no sub-sampling, and a padding rule that maps in-range positions to themselves (zero and reflect both
+// do: map_virtual only touches positions outside the image).
+static bool wino_upz(const DvcConvDesc* d) {
+    return d->in_up == 2 && d->in_sub == 1 && d->dil == 1 && d->pad == 1 && d->stride == 1 && d->ksize == 3 &&
+           (d->pad_mode == DVC_PAD_ZERO || d->pad_mode == DVC_PAD_REFLECT);
+}
+
 static int wino_run(const DvcConvDesc* d, const DvcConvDesc* d2, const float* x, const float* x2, const float* u_packed,
                     const float* bias, const float* act_slope_ptr, const float* residual, float* y, void* workspace,
                     size_t workspace_bytes, dvcStream stream, float* pool = nullptr, long pool_batch_stride = 0) {
@@ -713,7 +722,7 @@ static int wino_run(const DvcConvDesc* d, const DvcConvDesc* d2, const float* x,
         a.res = residual ? residual + (long)n0 * a.res_bs : nullptr;
         DVC_REQUIRE((long)s.gx * s.gy * NB * a.split < (1L << 31), "dvc_conv2d_winograd: grid too large");
         const dim3 grid = wino_finish_grid(s, NB);
-        if (d2) conv_wino_launch_m1_dual(best_tr, grid, st, s);
+        if (d2) conv_wino_launch_m1_dual(best_tr, wino_upz(d), grid, st, s);
         else if (best_m == 0) conv_wino_launch_m4(best_tr, grid, st, s);
         else if (best_m == 1) conv_wino_launch_m2(best_tr, grid, st, s);
         else if (best_m == 2) conv_wino_launch_m1(best_tr, grid, st, s);

@@ -116,6 +116,15 @@ __host__ __device__ constexpr int wino_pitch(int tr) { return tr == 1 ? 66 : tr 
                    "i"(1 * (PITCH / 2) + 1), "i"(2 * (PITCH / 2)), "i"(2 * (PITCH / 2) + 1), "i"((UOFS) + 0),           \
                    "i"((UOFS) + 512)                                                                                    \
                  : "memory")
+// ... of wave half 1 in a K-step of zero-position (UPZ) channels: patch rows 1 and 3 and filter row 3 only, into the same registers
+#define WINO_LOADS_ROW3(D, U, XA, UA, UOFS)                                                                            \
+    asm volatile("ds_read2_b64 %0, %3 offset0:%5 offset1:%6\n\t"                                                        \
+                 "ds_read2_b64 %1, %3 offset0:%7 offset1:%8\n\t"                                                        \
+                 "ds_read_b128 %2, %4 offset:%9"                                                                        \
+                 : "=&v"(D[0]), "=&v"(D[2]), "=&v"(U[1])                                                                \
+                 : "v"(XA), "v"(UA), "i"(0 * (PITCH / 2)), "i"(0 * (PITCH / 2) + 1), "i"(2 * (PITCH / 2)),              \
+                   "i"(2 * (PITCH / 2) + 1), "i"((UOFS) + 512)                                                          \
+                 : "memory")
 // The loads above are asynchronous and the compiler does not know it: every later use of their destination registers must
 // depend on this statement (the registers pass through it), otherwise the compiler is free to move a use — or a register
 // copy — in front of the wait.
@@ -156,7 +165,18 @@ __host__ __device__ constexpr int wino_us_floats(int wm, int kc) { return wm * k
 // SA = ConvWinoArgs in the address space the caller holds it in: generic (a by-value kernel argument) or the kernel-argument
 // segment itself (address space 4, the group kernel's item table: every field read stays a scalar load from constant memory —
 // a generic reference to a dynamically selected item makes the compiler copy the whole table to scratch).
-template <int WM, int WN, int TR, int KC, int VAR = 0, bool DUAL = false, class SA = ConvWinoArgs>
+//
+// UPZ (DUAL launches whose first input is read through in_up == 2 at dilation 1; the launcher checks the conditions): for those
+// channels a lane's 4x4 patch is d = [a, b, b, c] in both directions — tile origins are even and pad is 1, so patch rows / columns
+// 1 and 2 are the SAME stored element, whatever rows 0 and 3 are (neighbour, reflection or the padding zero).  Row 2 of B^T d is
+// d2 - d1 and column 2 of t B is z - y: a float minus a bit-identical copy of itself, exactly +0.  So the 7 transform positions
+// (2, *) and (*, 2) of every such channel are +0, and their MFMAs add U * 0 = +-0 to accumulators that are +0 when the first input's
+// chunks run (they come first in every split range): a bitwise no-op for finite operands.  The K loop is split at the input
+// boundary and the first part leaves those MFMAs out — half 0 issues 6 of its 8 per K-step, half 1 (row 3 only) 3 — together with
+// the loads and transform arithmetic that fed nothing else.  Position ownership, the order of every remaining sum, the inverse
+// transform and the exchange are unchanged: the output bits are those of the full loop.  (Tiles wholly outside the image may
+// see unequal rows under reflect padding; their outputs are never stored.)
+template <int WM, int WN, int TR, int KC, int VAR = 0, bool DUAL = false, class SA = ConvWinoArgs, bool UPZ = false>
 __device__ __forceinline__ void conv_wino_body(const SA& s, const int wlog, float* const xsb, float* const usb) {
 #if defined(__HIP_DEVICE_COMPILE__)
     const auto& a = s.k;
@@ -181,6 +201,7 @@ __device__ __forceinline__ void conv_wino_body(const SA& s, const int wlog, floa
     constexpr int KS = KC / 2;
     constexpr int NBUF = WINO_NBUF;
     constexpr int OOB = (int)0x80000000;
+    static_assert(!UPZ || DUAL, "the zero-position form is built for the two-input launches");
     static_assert(NBUF * UQ * 4 >= 2 * NPAIR * 32 * 64, "the output exchange fits in the filter buffers");
 
     const int tid = threadIdx.x;
@@ -264,11 +285,12 @@ __device__ __forceinline__ void conv_wino_body(const SA& s, const int wlog, floa
     if (DUAL)
         rs_x2 = __builtin_amdgcn_make_buffer_rsrc((void*)(s.x2 + (long)n * s.x2_bs), 0, (a.Cin - cinA) * HWi2 * 4, 0x00020000);
     const int nchA = cinA / KC;
-    auto issue_x = [&](int c, int buf) {
+    // X2C: every chunk this call site can issue belongs to the second input (the second part of a UPZ K loop) — no selection
+    auto issue_x = [&](int c, int buf, auto X2C) {
         float* xs = xsb + buf * C_XS;
         // (DUAL: descriptor, scalar offset and lane offsets SELECTED, not branched on — the K loop stays one basic block, which
         // is what its hand-placed interleaving of DMA issue and MFMAs relies on)
-        const bool first = !DUAL || c < nchA;
+        const bool first = !decltype(X2C)::value && (!DUAL || c < nchA);
         const __amdgpu_buffer_rsrc_t rs = first ? rs_x : rs_x2;
         const int sx = first ? c * KC * HWi * 4 : (c - nchA) * KC * HWi2 * 4;
 #pragma unroll
@@ -277,10 +299,11 @@ __device__ __forceinline__ void conv_wino_body(const SA& s, const int wlog, floa
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (CONV_AS3 void*)(xs + t * NT + wave * 64), 4, go, sx, 0, 0);
         }
     };
-    auto issue = [&](int c, int buf) {
-        issue_x(c, buf);
+    auto issue = [&](int c, int buf, auto X2C) {
+        issue_x(c, buf, X2C);
         issue_w(c, buf);
     };
+    constexpr std::false_type ANY_INPUT{};
 
     // LDS byte addresses of the lane's operands inside buffer 0: patch rows ph .. ph + 2 of its tile, filter rows 2 ph, 2 ph + 1
     const unsigned xlane =
@@ -291,14 +314,14 @@ __device__ __forceinline__ void conv_wino_body(const SA& s, const int wlog, floa
     // buffer nobody reads any more, once the range is exhausted — so the waits are compile-time constants and the K loop is
     // one basic block (VAR 3 keeps the conditional issues / waits it replaced, for A/B: profiles/r03_conv_wino_branch_free.txt)
     constexpr bool BRANCH_FREE = VAR != 3;
-    issue_x(c_begin, 0);      // (the chunk's filter half is already in flight; NI instructions per chunk either way)
+    issue_x(c_begin, 0, ANY_INPUT);      // (the chunk's filter half is already in flight; NI instructions per chunk either way)
     if (BRANCH_FREE) {
-        issue(min(c_begin + 1, c_end - 1), 1);
-        issue(min(c_begin + 2, c_end - 1), 2);
+        issue(min(c_begin + 1, c_end - 1), 1, ANY_INPUT);
+        issue(min(c_begin + 2, c_end - 1), 2, ANY_INPUT);
         asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NI) : "memory");
     } else {
-        if (c_begin + 1 < c_end) issue(c_begin + 1, 1);
-        if (c_begin + 2 < c_end) issue(c_begin + 2, 2);
+        if (c_begin + 1 < c_end) issue(c_begin + 1, 1, ANY_INPUT);
+        if (c_begin + 2 < c_end) issue(c_begin + 2, 2, ANY_INPUT);
         if (c_begin + 2 < c_end) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NI) : "memory");
         else if (c_begin + 1 < c_end) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NI) : "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -320,7 +343,8 @@ __device__ __forceinline__ void conv_wino_body(const SA& s, const int wlog, floa
         auto lo = [](const f32x4& v) { return __builtin_shufflevector(v, v, 0, 1); };
         auto hh = [](const f32x4& v) { return __builtin_shufflevector(v, v, 2, 3); };
         // (B^T d) rows 2 PH, 2 PH + 1:  PH 0: d0 - d2, d1 + d2   PH 1: d2 - d1, d1 - d3
-        auto transform_a = [&](const f32x4 (&d)[3], f32x2 (&tl)[2], f32x2 (&th)[2]) {
+        // (row3_only, half 1 only: its row 2 feeds nothing in the next K-step)
+        auto transform_a = [&](const f32x4 (&d)[3], f32x2 (&tl)[2], f32x2 (&th)[2], const bool row3_only = false) {
             if (VAR == 1) {
                 // the same 16 additions, one lane-wide instruction each (MI355X_MICROARCH.md: a packed fp32 VALU beside
                 // MFMAs costs more than the scalar pair)
@@ -330,8 +354,10 @@ __device__ __forceinline__ void conv_wino_body(const SA& s, const int wlog, floa
                     WINO_S_ADD(tl[1].x, d[1].x, d[2].x); WINO_S_ADD(tl[1].y, d[1].y, d[2].y);
                     WINO_S_ADD(th[1].x, d[1].z, d[2].z); WINO_S_ADD(th[1].y, d[1].w, d[2].w);
                 } else {
-                    WINO_S_SUB(tl[0].x, d[1].x, d[0].x); WINO_S_SUB(tl[0].y, d[1].y, d[0].y);
-                    WINO_S_SUB(th[0].x, d[1].z, d[0].z); WINO_S_SUB(th[0].y, d[1].w, d[0].w);
+                    if (!row3_only) {
+                        WINO_S_SUB(tl[0].x, d[1].x, d[0].x); WINO_S_SUB(tl[0].y, d[1].y, d[0].y);
+                        WINO_S_SUB(th[0].x, d[1].z, d[0].z); WINO_S_SUB(th[0].y, d[1].w, d[0].w);
+                    }
                     WINO_S_SUB(tl[1].x, d[0].x, d[2].x); WINO_S_SUB(tl[1].y, d[0].y, d[2].y);
                     WINO_S_SUB(th[1].x, d[0].z, d[2].z); WINO_S_SUB(th[1].y, d[0].w, d[2].w);
                 }
@@ -343,8 +369,10 @@ __device__ __forceinline__ void conv_wino_body(const SA& s, const int wlog, floa
                 WINO_PK_ADD(tl[1], lo(d[1]), lo(d[2]));
                 WINO_PK_ADD(th[1], hh(d[1]), hh(d[2]));
             } else {
-                WINO_PK_SUB(tl[0], lo(d[1]), lo(d[0]));
-                WINO_PK_SUB(th[0], hh(d[1]), hh(d[0]));
+                if (!row3_only) {
+                    WINO_PK_SUB(tl[0], lo(d[1]), lo(d[0]));
+                    WINO_PK_SUB(th[0], hh(d[1]), hh(d[0]));
+                }
                 WINO_PK_SUB(tl[1], lo(d[0]), lo(d[2]));
                 WINO_PK_SUB(th[1], hh(d[0]), hh(d[2]));
             }
@@ -372,8 +400,14 @@ __device__ __forceinline__ void conv_wino_body(const SA& s, const int wlog, floa
         // operands (set `ns`) are issued among them.  The last K-step of a chunk crosses into the next chunk: wait for that
         // chunk's DMA (issued two chunks ago), barrier (every wave has also finished reading the current buffer: its
         // last reads were awaited one K-step earlier), refill the current buffer with chunk c+3.
+        // ZC: the chunk's channels have the zero positions (UPZ, first input): half 0 leaves out column 2 (k = 2, 6), half 1 its
+        // whole row 2 (k = 0 .. 3) and column 2 of row 3 (k = 6); the accumulators of the skipped positions keep their value.
+        // Within such a chunk half 1 prepares row 3 only; every chunk's LAST K-step prepares the full operand set, the next
+        // chunk may be the second input's.  X2C: see issue_x.
         int buf = 0;
-        for (int c = c_begin; c < c_end; ++c) {
+        auto chunk = [&](auto ZC, auto X2C, const int c) {
+            constexpr bool Z = decltype(ZC)::value;
+            constexpr bool M0 = !(Z && PH == 1), MC2 = !Z;      // issue row 2 PH at all | issue column 2
             const unsigned xb = xlane + buf * (C_XS * 4), ub = ulane + buf * (UQ * 16);
             const int nbuf = buf == NBUF - 1 ? 0 : buf + 1;
             const unsigned xbn = xlane + nbuf * (C_XS * 4), ubn = ulane + nbuf * (UQ * 16);
@@ -382,41 +416,51 @@ __device__ __forceinline__ void conv_wino_body(const SA& s, const int wlog, floa
             for (int ks = 0; ks < KS; ++ks) {
                 const int cs = ks & 1, ns = cs ^ 1;
                 const bool last = ks == KS - 1;
+                const bool row3_only = Z && PH == 1 && !last;
                 f32x2 tl[2], th[2];
-                WINO_MFMA(0, U[cs][0].x, V03[cs][0].x);
+                if (M0) WINO_MFMA(0, U[cs][0].x, V03[cs][0].x);
                 if (!last) {
-                    WINO_LOADS(D[ns], U[ns], xb + (ks + 1) * (2 * plane * 4), ub, (ks + 1) * 4096);
+                    if (row3_only) WINO_LOADS_ROW3(D[ns], U[ns], xb + (ks + 1) * (2 * plane * 4), ub, (ks + 1) * 4096);
+                    else WINO_LOADS(D[ns], U[ns], xb + (ks + 1) * (2 * plane * 4), ub, (ks + 1) * 4096);
                 } else if (BRANCH_FREE) {
                     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NI) : "memory");
                     __builtin_amdgcn_s_barrier();
-                    issue(min(c + 3, c_end - 1), buf);
+                    issue(min(c + 3, c_end - 1), buf, X2C);
                     WINO_LOADS(D[ns], U[ns], xbn, ubn, 0);
                 } else if (more) {
                     if (c + 2 < c_end) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NI) : "memory");
                     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                     __builtin_amdgcn_s_barrier();
-                    if (c + 3 < c_end) issue(c + 3, buf);
+                    if (c + 3 < c_end) issue(c + 3, buf, X2C);
                     WINO_LOADS(D[ns], U[ns], xbn, ubn, 0);
                 }
                 __builtin_amdgcn_sched_barrier(0);
-                WINO_MFMA(1, U[cs][0].y, V12[cs][0].x);
-                WINO_MFMA(2, U[cs][0].z, V12[cs][0].y);
-                WINO_MFMA(3, U[cs][0].w, V03[cs][0].y);
+                if (M0) WINO_MFMA(1, U[cs][0].y, V12[cs][0].x);
+                if (M0 && MC2) WINO_MFMA(2, U[cs][0].z, V12[cs][0].y);
+                if (M0) WINO_MFMA(3, U[cs][0].w, V03[cs][0].y);
                 WINO_WAIT_LOADS(D[ns], U[ns]);
                 __builtin_amdgcn_sched_barrier(0);
-                transform_a(D[ns], tl, th);
+                transform_a(D[ns], tl, th, row3_only);
                 __builtin_amdgcn_sched_barrier(0);
                 WINO_MFMA(4, U[cs][1].x, V03[cs][1].x);
-                transform_b(tl[0], th[0], V03[ns][0], V12[ns][0]);
+                if (!row3_only) transform_b(tl[0], th[0], V03[ns][0], V12[ns][0]);
                 __builtin_amdgcn_sched_barrier(0);
                 WINO_MFMA(5, U[cs][1].y, V12[cs][1].x);
                 transform_b(tl[1], th[1], V03[ns][1], V12[ns][1]);
                 __builtin_amdgcn_sched_barrier(0);
-                WINO_MFMA(6, U[cs][1].z, V12[cs][1].y);
+                if (MC2) WINO_MFMA(6, U[cs][1].z, V12[cs][1].y);
                 WINO_MFMA(7, U[cs][1].w, V03[cs][1].y);
                 __builtin_amdgcn_sched_barrier(0);
             }
             buf = nbuf;
+        };
+        if (UPZ) {
+            // the first input's chunks of this workgroup's range, then the second's: either part may be empty (split-K ranges)
+            const int c_mid = min(c_end, max(c_begin, nchA));
+            for (int c = c_begin; c < c_mid; ++c) chunk(std::true_type{}, std::false_type{}, c);
+            for (int c = c_mid; c < c_end; ++c) chunk(std::false_type{}, std::true_type{}, c);
+        } else {
+            for (int c = c_begin; c < c_end; ++c) chunk(std::false_type{}, std::false_type{}, c);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();       // every wave is done with the staging buffers: the exchange may overwrite them
@@ -526,7 +570,7 @@ __device__ __forceinline__ void conv_wino_body(const SA& s, const int wlog, floa
 #endif
 }
 
-template <int WM, int WN, int TR, int KC, int VAR = 0, bool DUAL = false>
+template <int WM, int WN, int TR, int KC, int VAR = 0, bool DUAL = false, bool UPZ = false>
 __global__ __launch_bounds__(128 * WM * WN) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv_wino_kernel(ConvWinoArgs s) {
     __shared__ __attribute__((aligned(16))) float xsb[WINO_NBUF * wino_xs_floats(WM, WN, TR, KC)];
     __shared__ __attribute__((aligned(16))) float usb[WINO_NBUF * wino_us_floats(WM, KC)];
@@ -537,7 +581,7 @@ __global__ __launch_bounds__(128 * WM * WN) __attribute__((amdgpu_waves_per_eu(2
     const int G = s.gx * s.gy * s.gz;
     const int xq = G / 8, xr = G % 8, xcd = blockIdx.x % 8, xi = blockIdx.x / 8;
     const int wlog = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + xi;
-    conv_wino_body<WM, WN, TR, KC, VAR, DUAL>(s, wlog, xsb, usb);
+    conv_wino_body<WM, WN, TR, KC, VAR, DUAL, ConvWinoArgs, UPZ>(s, wlog, xsb, usb);
 }
 
 // ---- several INDEPENDENT layers in one launch (dvc_conv2d_winograd_group): WarpNet's four heads (NonlocalNet.py:451-458) are
@@ -633,9 +677,19 @@ static void conv_wino_launch_shape(int tr, dim3 grid, hipStream_t st, const Conv
     }
 }
 
+// upz: the first input's transform positions (2, *) and (*, 2) are exactly zero (conv_wino_body; decided by wino_setup)
 template <int WM, int WN, int KC>
-static void conv_wino_launch_shape_dual(int tr, dim3 grid, hipStream_t st, const ConvWinoArgs& s) {
+static void conv_wino_launch_shape_dual(int tr, bool upz, dim3 grid, hipStream_t st, const ConvWinoArgs& s) {
     constexpr int NT = 128 * WM * WN;
+    if (upz) {
+        switch (tr) {
+            case 1: hipLaunchKernelGGL((conv_wino_kernel<WM, WN, 1, KC, 0, true, true>), grid, dim3(NT), 0, st, s); break;
+            case 2: hipLaunchKernelGGL((conv_wino_kernel<WM, WN, 2, KC, 0, true, true>), grid, dim3(NT), 0, st, s); break;
+            case 4: hipLaunchKernelGGL((conv_wino_kernel<WM, WN, 4, KC, 0, true, true>), grid, dim3(NT), 0, st, s); break;
+            default: hipLaunchKernelGGL((conv_wino_kernel<WM, WN, 8, KC, 0, true, true>), grid, dim3(NT), 0, st, s); break;
+        }
+        return;
+    }
     switch (tr) {
         case 1: hipLaunchKernelGGL((conv_wino_kernel<WM, WN, 1, KC, 0, true>), grid, dim3(NT), 0, st, s); break;
         case 2: hipLaunchKernelGGL((conv_wino_kernel<WM, WN, 2, KC, 0, true>), grid, dim3(NT), 0, st, s); break;
@@ -644,7 +698,7 @@ static void conv_wino_launch_shape_dual(int tr, dim3 grid, hipStream_t st, const
     }
 }
 
-void conv_wino_launch_m1_dual(int tr, dim3 grid, hipStream_t st, const ConvWinoArgs& s);   // the two-input form, 64 x 32 shape only
+void conv_wino_launch_m1_dual(int tr, bool upz, dim3 grid, hipStream_t st, const ConvWinoArgs& s);   // the two-input form, 64 x 32 shape only
 void conv_wino_launch_m4(int tr, dim3 grid, hipStream_t st, const ConvWinoArgs& s);   // 128 channels x 32 tiles, 8 waves
 void conv_wino_launch_m2(int tr, dim3 grid, hipStream_t st, const ConvWinoArgs& s);   // 64 channels x 64 tiles, 8 waves
 void conv_wino_launch_m1(int tr, dim3 grid, hipStream_t st, const ConvWinoArgs& s);   // 64 channels x 32 tiles, 4 waves, two per CU
