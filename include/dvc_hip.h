@@ -278,7 +278,9 @@ typedef struct DvcInstNormItem {
 } DvcInstNormItem;
 int dvc_instnorm_apply_group(const DvcInstNormItem* items, int32_t n_items, dvcStream stream);
 
-/* nn.MaxPool2d(2,2) floor mode, NonlocalNet.py:237-255. planes = N*C. */
+/* nn.MaxPool2d(2,2) floor mode, NonlocalNet.py:237-255. planes = N*C.
+ * NaN: the window maximum is taken with fmaxf, which DROPS a NaN (the maximum of the other elements; NaN only when all four
+ * are), where ATen lets a NaN take the window.  The fused epilogue of dvc_conv2d_winograd_pool is tied to this bit for bit. */
 int dvc_maxpool2x2(const float* x, int32_t planes, int32_t H, int32_t W, float* y, dvcStream stream);
 /* nn.AvgPool2d(2,2): the pool="avg" variant of VGG19_pytorch, NonlocalNet.py:221-226; also, bit for bit,
  * F.interpolate(x, scale_factor=0.5, mode="bilinear") — full-resolution Lab -> network resolution, test.py:58,71. */

@@ -545,3 +545,22 @@ def test_conv_and_layer_records_are_what_they_were(monkeypatch):
     ops.conv3x3(T(1, 8, 20, 30), T(16, 8, 3, 3), lambda kind: T(8, 9, 16), None, layer="x.y")
     assert ops.layer_record == LAYER_RECORDS
     assert "algo" not in ops.conv_record[-1]                        # (the 8 -> 16 layer went to the general engine)
+
+
+def test_instnorm_fma_form_error_bound_is_satisfiable():
+    """The bound tests/test_gpu_glue_edges.py asserts of the InstanceNorm kernels over the mean / sigma sweep, checked here on
+    the same inputs against a numpy emulation of a CORRECT y = fma(x, sc, sh) (float32-rounded sc and sh, one rounding of the
+    result): the bound 2^-23 * (max|x| * rstd + max|y| + 1) holds for every ratio, so a kernel that misses it is wrong."""
+    import numpy as np
+
+    import instnorm_bound as IB
+    errs = []
+    for R in IB.RATIOS:
+        x = IB.sweep_plane(R)
+        y, rstd, mean = IB.reference(x)
+        assert abs(mean - R) < 0.1 and abs(rstd - 1.0) < 0.05       # the sweep is what it says: sigma = 1, mean = R
+        err = np.abs(IB.emulate_fma(x).astype(np.float64) - y).max()
+        assert err <= IB.bound(x), (R, err, IB.bound(x))
+        errs.append(err)
+    # the error of this form grows with the ratio (ATen's (x - mean) * rstd stays at an ulp of y): the bound is not idle
+    assert errs[-1] > 20 * errs[0]
