@@ -1,12 +1,13 @@
 """Drop-in for /root/reference/models/NonlocalNet.py.  The hot-path classes (test.py:19 imports `VGG19_pytorch, WarpNet`)
-live in dvc_amd.nets, the training side's non-local smoothness term `NonlocalWeightedAverage` in dvc_amd.nonlocal_avg,
-all MI355X HIP implementations.  Every other name of the reference's file (`WeightedAverage`, `WeightedAverage_color`,
-`find_local_patch`, the GAN and VGG helpers) is forwarded, on first use, to the next `models/NonlocalNet.py` on
-`models.__path__` — the reference's own file, loaded unmodified."""
+live in dvc_amd.nets, the training side's smoothness terms `NonlocalWeightedAverage` in dvc_amd.nonlocal_avg and
+`WeightedAverage_color` in dvc_amd.local_avg, all MI355X HIP implementations.  Every other name of the reference's file
+(`WeightedAverage`, `find_local_patch`, the GAN and VGG helpers) is forwarded, on first use, to the next
+`models/NonlocalNet.py` on `models.__path__` — the reference's own file, loaded unmodified."""
 import importlib.util as _ilu
 import os as _os
 import sys as _sys
 
+from dvc_amd.local_avg import WeightedAverage_color  # noqa: F401
 from dvc_amd.nets import VGG19_pytorch, WarpNet  # noqa: F401
 from dvc_amd.nonlocal_avg import NonlocalWeightedAverage  # noqa: F401
 

@@ -498,6 +498,28 @@ int dvc_nlwa_fwd(const float* x_lab, int32_t Cx, int32_t Hx, int32_t Wx, const f
                  float alpha, float* out, void* workspace, size_t workspace_bytes, dvcStream stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Local weighted average (models/NonlocalNet.py, WeightedAverage_color; find_local_patch :12-17), the local half of the
+ * training-side smoothness term, forward and backward — csrc/local_avg.hip, one launch each.  With r = patch_size / 2,
+ * g = (L + l_offset, a, b) of the nearest-resized x_lab and v = (a', b') of pred, both zero outside the image, per pixel p
+ * and offset d in [-r, r]^2:
+ *     w_d(p) = softmax_d(-|g(p + d) - g(p)|^2 / alpha)   (over all k*k offsets)      y_c(p) = sum_d w_d(p) v_c(p + d)
+ * x_lab [B][Cx >= 3][Hx][Wx] (channels 0..2 are read), scale_x*: the source-index scales of its nearest resize to H x W as
+ * for dvc_nlwa_fwd (1.0 and Hx == H, Wx == W: no resize).  pred [B][Cp][H][W]: channels ab_ch, ab_ch + 1 are a', b' (1 for
+ * a Lab tensor, 0 for a bare [B][2][H][W] ab tensor).  l_offset: 50 folds uncenter_l.  patch_size odd, 1..7; alpha > 0 and
+ * finite.  y [B][2][H][W].  All fp32 contiguous; no workspace, nothing k*k-times unfolded is materialised.
+ * dvc_lwa_bwd: for G [B][2][H][W] and the forward's y, d_pred_ab [B][2][H][W] = dy/dv^T G and, unless d_guide is NULL,
+ * d_guide [B][3][H][W] = the gradient of x_lab's channels 0..2 (the offset's derivative is 1); it is refused unless x_lab is
+ * unresized (Hx == H, Wx == W, both scales 1.0): a caller that wants it through a resize resizes first.
+ * Deterministic (gather form, no atomics); an image's result does not depend on B.  Bad arguments are reported before
+ * any launch. */
+int dvc_lwa_fwd(const float* x_lab, int32_t Cx, int32_t Hx, int32_t Wx, const float* pred, int32_t Cp, int32_t ab_ch, int32_t B,
+                int32_t H, int32_t W, float scale_xh, float scale_xw, float l_offset, int32_t patch_size, float alpha, float* y,
+                dvcStream stream);
+int dvc_lwa_bwd(const float* x_lab, int32_t Cx, int32_t Hx, int32_t Wx, const float* pred, int32_t Cp, int32_t ab_ch, int32_t B,
+                int32_t H, int32_t W, float scale_xh, float scale_xw, float l_offset, int32_t patch_size, float alpha,
+                const float* G, const float* y, float* d_pred_ab, float* d_guide, dvcStream stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Input gradient of VGG19_pytorch (frozen weights) and of tensor_lab2rgb — csrc/vgg_bwd.hip.  The 3x3 convolutions' input
  * gradients run on dvc_conv2d / dvc_conv2d_winograd / dvc_conv2d_ws with the transposed, flipped filters; these are the steps
  * between them.  Masks and routes follow ATen: threshold_backward(grad, relu_out, 0) zeroes the gradient where out <= 0;
