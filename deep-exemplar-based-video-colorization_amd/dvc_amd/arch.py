@@ -9,7 +9,14 @@ Shapes follow the reference constructors:
   VGG19_pytorch   /root/reference/models/NonlocalNet.py:197-226
   WarpNet         /root/reference/models/NonlocalNet.py:358-425
   ColorVidNet     /root/reference/models/ColorVidNet.py:7-94
+
+Next to each table stands what the layer walks of ``nets.py`` need to know about its structure (VGG_POOL_AFTER,
+WARP_HEAD_PLAN, CVN_GRAPH): derived once, here, immutable, and free of torch, so the relations can be read and tested
+without a device.
 """
+from collections import namedtuple
+from types import MappingProxyType
+from typing import NamedTuple
 
 # ---------------------------------------------------------------------------------------------
 # VGG19: 16 conv3x3 (pad 1) + ReLU, 5 maxpool2x2.  (name, cin, cout)
@@ -25,6 +32,8 @@ VGG_KEYS = [
     "r11", "r12", "p1", "r21", "r22", "p2", "r31", "r32", "r33", "r34", "p3",
     "r41", "r42", "r43", "r44", "p4", "r51", "r52", "r53", "r54", "p5",
 ]
+VGG_CONV_OF = MappingProxyType({"r" + n[4:].replace("_", ""): n for n, _, _ in VGG_CONVS})    # output key "r12" -> "conv1_2"
+VGG_POOL_AFTER = frozenset(k for k, nxt in zip(VGG_KEYS, VGG_KEYS[1:]) if k[0] == "r" and nxt[0] == "p")
 
 # ---------------------------------------------------------------------------------------------
 # WarpNet feature heads: list of (state_dict conv index, cin, cout, stride, prelu index).
@@ -40,6 +49,47 @@ WARP_HEAD_ORDER = ["layer2_1", "layer3_1", "layer4_1", "layer5_1"]
 WARP_FEATURE_CH = 64
 WARP_TRUNK_CH = 256          # 4 heads x 64 channels, also theta/phi inter_channels
 WARP_NUM_RESBLOCKS = 3
+
+
+# One head as WarpNet._heads walks it: conv_a -> norm + PReLU prelu_a -> [x2 up_mid] -> conv_b (stride_b) -> norm + PReLU prelu_b
+# -> [x2 up_out]; conv_* / prelu_* are positions in the head's Sequential.  (The first convolution's stride is 1 in every head.)
+WarpHead = namedtuple("WarpHead", "index name conv_a prelu_a conv_b stride_b prelu_b up_mid up_out")
+
+
+def _warp_head(index, name):
+    (ia, _, _, _, pa), (ib, _, _, sb, pb) = WARP_HEADS[name]["convs"]
+    return WarpHead(index, name, ia, pa, ib, sb, pb, WARP_HEADS[name]["up_mid"], WARP_HEADS[name]["up_out"])
+
+
+WARP_HEAD_PLAN = tuple(_warp_head(i, name) for i, name in enumerate(WARP_HEAD_ORDER))
+
+
+def warp_head_out_hw(name, H, W):
+    """Output size of the head `name` on an H x W feature map (the 3x3 convolutions reflect-pad by 1: only the stride and the
+    two upsamples move the size)."""
+    hd = WARP_HEAD_PLAN[WARP_HEAD_ORDER.index(name)]
+    if hd.up_mid:
+        H, W = 2 * H, 2 * W
+    H, W = (H - 1) // hd.stride_b + 1, (W - 1) // hd.stride_b + 1
+    if hd.up_out:
+        H, W = 2 * H, 2 * W
+    return H, W
+
+
+def warp_trunk_geometry(shapes_in):
+    """(h, w, rpad5) of the trunk tensor from the (H, W) of the four heads' inputs, in WARP_HEAD_ORDER.  rpad5 = 1: layer5_1's
+    output is short of layer2_1's and gets one replicated row top and bottom (NonlocalNet.py:461-463)."""
+    shapes = [warp_head_out_hw(name, H, W) for name, (H, W) in zip(WARP_HEAD_ORDER, shapes_in)]
+    h, w = shapes[0]
+    rpad5 = 0
+    if shapes[3] != shapes[0]:
+        rpad5 = 1
+        shapes[3] = (shapes[3][0] + 2, shapes[3][1])
+    for nm, sh in zip(WARP_HEAD_ORDER, shapes):
+        if sh != (h, w):
+            raise RuntimeError(f"Sizes of tensors must match except in dimension 1: {nm} gives {sh}, "
+                               f"layer2_1 gives {(h, w)}")
+    return h, w, rpad5
 
 
 def warpnet_param_shapes():
@@ -117,7 +167,58 @@ CVN_CONVS = [
     dict(key="conv10_2", cin=128, cout=128, dil=1, src="c10_1", pre=None, add=None, act="leaky", dst="c10_2"),
 ]
 CVN_SS = [("conv1_2norm_ss", 64), ("conv2_2norm_ss", 128), ("conv3_3norm_ss", 256)]
-CVN_OUT = dict(key="conv10_ab", cin=128, cout=2)   # 1x1 conv then tanh*128 (ColorVidNet.py:142-144)
+CVN_OUT = dict(key="conv10_ab", cin=128, cout=2, src="c10_2")   # 1x1 conv then tanh*128 (ColorVidNet.py:142-144)
+
+
+class CvnGraph(NamedTuple):
+    """Who reads what in CVN_CONVS + CVN_OUT, for ColorVidNet's forward and backward walks.  "Activation" = a `dst` name."""
+    by_key: MappingProxyType            # conv key -> its entry (read-only view)
+    by_dst: MappingProxyType            # activation -> the entry that produces it
+    norm_variants: MappingProxyType     # activation -> the InstanceNorm forms to materialise right after it is produced, in
+                                        # consumer order without repeats: None = plain, or the `_ss` key (scaled, stride 2)
+    norm_pair: MappingProxyType         # activation -> `_ss` key where both forms are wanted: one launch produces the two
+    ss_of: MappingProxyType             # activation -> the `_ss` key that scales its norm
+    norm_only: frozenset                # activations read only through a norm: the producer may leave its split-K reduce to it
+    dual: MappingProxyType              # consumer key -> the key of the skip convolution it adds, where the two can run as ONE
+                                        # launch: a linear convolution read by nothing else, same dilation
+    skip_keys: frozenset                # those skip convolutions: they run with their consumer, not at their place in the table
+    adder: MappingProxyType             # skip output -> the activation of the block it is added into
+    grad_kind: MappingProxyType         # `pre` -> the slot of cvn_inorm_bwd a consumer's input gradient goes to ("raw": no norm)
+    saved_acts: tuple                   # activations behind a nonlinearity: what the backward needs saved
+
+
+def _cvn_graph(convs, out):
+    by_key = {c["key"]: MappingProxyType(c) for c in convs}
+    by_dst = {c["dst"]: by_key[c["key"]] for c in convs}
+    norm_uses, raw_use, uses = {}, {out["src"]}, {}
+    for c in convs:
+        if c["pre"] is None:
+            raw_use.add(c["src"])
+        else:
+            norm_uses.setdefault(c["src"], []).append(c["ss"] if c["pre"] == "norm_ss" else None)
+        if c["add"] is not None:
+            raw_use.add(c["add"])
+        for a in (c["src"], c["add"]):
+            uses[a] = uses.get(a, 0) + 1
+    norm_variants = {a: tuple(dict.fromkeys(v)) for a, v in norm_uses.items()}
+    ss_of = {c["src"]: c["ss"] for c in convs if c["pre"] == "norm_ss"}
+    dual = {}
+    for c in convs:
+        e = by_dst.get(c["add"])
+        if e is not None and e["act"] == "none" and e["add"] is None and uses[e["dst"]] == 1 and e["dil"] == c["dil"] \
+                and e["pre"] in (None, "norm") and c["pre"] in ("up", "norm", None):
+            dual[c["key"]] = e["key"]
+    ro = MappingProxyType
+    return CvnGraph(
+        by_key=ro(by_key), by_dst=ro(by_dst), norm_variants=ro(norm_variants),
+        norm_pair=ro({a: k for a, k in ss_of.items() if None in norm_variants[a]}), ss_of=ro(ss_of),
+        norm_only=frozenset(norm_uses) - raw_use, dual=ro(dual), skip_keys=frozenset(dual.values()),
+        adder=ro({c["add"]: c["dst"] for c in convs if c["add"] is not None}),
+        grad_kind=ro({None: "raw", "norm": "full", "norm_ss": "ss", "up": "up"}),
+        saved_acts=tuple(c["dst"] for c in convs if c["act"] != "none"))
+
+
+CVN_GRAPH = _cvn_graph(CVN_CONVS, CVN_OUT)
 
 # state_dict key order of the reference module (registration order in ColorVidNet.__init__,
 # with conv8_1/9_1/10_1 re-registered in place as Sequential(Upsample, Conv2d)).

@@ -23,7 +23,6 @@ from torch.autograd.function import once_differentiable
 from . import arch, ops
 
 _VGG_MEAN_BGR = (0.40760392, 0.45795686, 0.48501961)  # utils/util.py:351
-_VGG_CONV_OF = {("r%s" % n[4:].replace("_", "")): n for n, _, _ in arch.VGG_CONVS}     # output key "r12" -> "conv1_2"
 
 
 _pack_epoch = 0
@@ -299,7 +298,7 @@ class VGG19_pytorch(nn.Module):
                 i, key = i - 1, rk
             else:
                 dZ = ops.vgg_act_bwd(g, g_ext.get(key), saved[key], out=g)
-            name = _VGG_CONV_OF[key]
+            name = arch.VGG_CONV_OF[key]
             if name == "conv1_1":
                 w = self.conv1_1.weight
                 wt = self._cache.get("vgg_bwd.conv1_1" + (":pre" if preprocess else ""), w,
@@ -310,6 +309,15 @@ class VGG19_pytorch(nn.Module):
             del dZ
             i -= 1
         return None
+
+    def _fuses_pool(self, key, i, last, cur, N):
+        """Does the convolution behind key `i` (input `cur`) also produce the max pool that follows it?  relu1_2 / relu2_2 /
+        relu3_4 / relu4_4 -> pool, when the pool is wanted and the layer goes to the Winograd kernel."""
+        name = arch.VGG_CONV_OF[key]
+        return (self._pool == "max" and ops.pool_fusion() and i + 1 <= last and key in arch.VGG_POOL_AFTER
+                and min(cur.shape[2:]) >= 2
+                and ops.winograd_selected(N, cur.shape[1], cur.shape[2], cur.shape[3], getattr(self, name).weight.shape[0],
+                                          layer="vgg." + name))
 
     def _forward(self, x, out_keys, preprocess, _gray, saved=None):
         """The layer walk.  saved: a dict that receives every convolution's post-ReLU output (the full-resolution tensor of a
@@ -329,20 +337,17 @@ class VGG19_pytorch(nn.Module):
                     cur, pooled = pooled, None
                 else:
                     cur = ops.maxpool2x2(cur) if self._pool == "max" else ops.avgpool2x2(cur)
-            elif (self._pool == "max" and ops.pool_fusion() and i + 1 <= last and arch.VGG_KEYS[i + 1][0] == "p"
-                  and min(cur.shape[2:]) >= 2
-                  and ops.winograd_selected(N, cur.shape[1], cur.shape[2], cur.shape[3], getattr(self, _VGG_CONV_OF[key]).weight.shape[0],
-                                            layer="vgg." + _VGG_CONV_OF[key])):
-                # relu1_2 / relu2_2 / relu3_4 / relu4_4 -> pool: the pooled tensor comes out of the convolution's own launch; the
-                # full-resolution one only when somebody asked for it
-                conv = getattr(self, _VGG_CONV_OF[key])
+            elif self._fuses_pool(key, i, last, cur, N):
+                # the pooled tensor comes out of the convolution's own launch; the full-resolution one only when somebody asked
+                # for it
+                name = arch.VGG_CONV_OF[key]
+                conv = getattr(self, name)
                 if ops.layer_record is not None:
-                    ops.record_layer("vgg." + _VGG_CONV_OF[key], cur.shape[1], conv.weight.shape[0], cur.shape[2], cur.shape[3])
-                cur, pooled = ops.conv2d_winograd_pool(cur, _packs(self._cache, _VGG_CONV_OF[key], conv.weight)("winograd"),
-                                                       conv.bias.detach(), act=ops.ACT_RELU,
-                                                       want_full=key in out_keys or saved is not None)
+                    ops.record_layer("vgg." + name, cur.shape[1], conv.weight.shape[0], cur.shape[2], cur.shape[3])
+                cur, pooled = ops.conv2d_winograd_pool(cur, _packs(self._cache, name, conv.weight)("winograd"), conv.bias.detach(),
+                                                       act=ops.ACT_RELU, want_full=key in out_keys or saved is not None)
             else:
-                name = _VGG_CONV_OF[key]
+                name = arch.VGG_CONV_OF[key]
                 conv = getattr(self, name)
                 bias = conv.bias.detach()
                 if name == "conv1_1" and preprocess:
@@ -448,10 +453,9 @@ class WarpNet(nn.Module):
 
     def prepare(self):
         """Pack every weight now, on the current stream (see _PackCache.get)."""
-        for name in arch.WARP_HEAD_ORDER:
-            seq = getattr(self, name)
-            for (ci, _, _, _, _) in arch.WARP_HEADS[name]["convs"]:
-                _prepack(self._cache, f"{name}.{ci}", seq[ci])
+        for hd in arch.WARP_HEAD_PLAN:
+            for ci in (hd.conv_a, hd.conv_b):
+                _prepack(self._cache, f"{hd.name}.{ci}", getattr(self, hd.name)[ci])
         for b in range(arch.WARP_NUM_RESBLOCKS):
             _prepack(self._cache, f"layer.{b}.conv1", self.layer[b].conv1)
             _prepack(self._cache, f"layer.{b}.conv2", self.layer[b].conv2)
@@ -466,72 +470,48 @@ class WarpNet(nn.Module):
         """The four heads of one side, concatenated: the `trunk` tensor [N,256,h,w] the residual blocks start from."""
         feats = [r2, r3, r4, r5]
         N = r2.shape[0]
-        dev = r2.device
-        # geometry of the four head outputs
-        shapes = []
-        for name, x in zip(arch.WARP_HEAD_ORDER, feats):
-            spec = arch.WARP_HEADS[name]
-            H, W = x.shape[2], x.shape[3]
-            if spec["up_mid"]:
-                H, W = 2 * H, 2 * W
-            s = spec["convs"][1][3]
-            H, W = (H - 1) // s + 1, (W - 1) // s + 1
-            if spec["up_out"]:
-                H, W = 2 * H, 2 * W
-            shapes.append((H, W))
-        h, w = shapes[0]
-        rpad5 = 0
-        if shapes[3] != shapes[0]:  # NonlocalNet.py:461-463 pads one replicated row top and bottom
-            rpad5 = 1
-            shapes[3] = (shapes[3][0] + 2, shapes[3][1])
-        for nm, sh in zip(arch.WARP_HEAD_ORDER, shapes):
-            if sh != (h, w):
-                raise RuntimeError(f"Sizes of tensors must match except in dimension 1: {nm} gives {sh}, "
-                                   f"layer2_1 gives {(h, w)}")
-        trunk = torch.empty((N, arch.WARP_TRUNK_CH, h, w), device=dev, dtype=torch.float32)
+        h, w, rpad5 = arch.warp_trunk_geometry([x.shape[2:] for x in feats])
+        trunk = torch.empty((N, arch.WARP_TRUNK_CH, h, w), device=r2.device, dtype=torch.float32)
         bs = arch.WARP_TRUNK_CH * h * w
         # The four heads are mutually independent (NonlocalNet.py:451-458): they advance stage by stage — first convolutions,
         # their norms, second convolutions, final norms into the trunk's channel slices — and each stage is ONE launch over the
         # heads that take the same kind of kernel (ops.conv3x3_group / ops.instnorm_apply_group: bit-identical to per-layer
         # launches, which DVC_GROUP_HEADS=0 brings back).  The stride-2 head (layer2_1, run-time-geometry direct kernel with
         # the norm applied on load) keeps its own launches.
-        heads = []
-        for i, (name, x) in enumerate(zip(arch.WARP_HEAD_ORDER, feats)):
-            spec = arch.WARP_HEADS[name]
-            seq = getattr(self, name)
-            (ia, _, _, _, pa), (ib, _, _, sb, pb) = spec["convs"]
-            heads.append(dict(i=i, name=name, spec=spec, seq=seq, ia=ia, pa=pa, ib=ib, sb=sb, pb=pb, ca=seq[ia], cb=seq[ib], x=x))
+        heads = arch.WARP_HEAD_PLAN
+        seqs = [getattr(self, hd.name) for hd in heads]
 
-        def conv_item(key, conv, x, **kw):
+        def conv_item(hd, ci, x, **kw):
+            key, conv = f"{hd.name}.{ci}", seqs[hd.index][ci]
             return dict(x=x, weight=conv.weight, packs=_packs(self._cache, key, conv.weight), bias=conv.bias.detach(),
                         layer="warp." + key, pad_mode=ops.PAD_REFLECT, **kw)
 
         # stage 1: first convolutions
-        t1 = ops.conv3x3_group([conv_item(f"{hd['name']}.{hd['ia']}", hd["ca"], hd["x"], defer_reduce=hd["sb"] == 1) for hd in heads])
+        t1 = ops.conv3x3_group([conv_item(hd, hd.conv_a, feats[hd.index], defer_reduce=hd.stride_b == 1) for hd in heads])
         # stage 2: InstanceNorm + PReLU, materialised (one launch for the four heads, in place where the convolution wrote a
         # tensor) so that the next convolution has no fused input transform.  r06: the stride-2 head too — up to r05 its
         # statistics were a launch of their own and the stride-2 convolution applied them on load; as an item of the grouped
         # launch the norm costs nothing extra, and the convolution (run-time-geometry kernel, register staging either way)
         # reads the normalised tensor
-        normed = ops.instnorm_apply_group([dict(x=t1[k], out=None if isinstance(t1[k], ops.ConvPartials) else t1[k],
-                                                slope_t=hd["seq"][hd["pa"]].weight.detach()) for k, hd in enumerate(heads)])
-        plain = [k for k, hd in enumerate(heads) if hd["sb"] == 1]
+        normed = ops.instnorm_apply_group([dict(x=t, out=None if isinstance(t, ops.ConvPartials) else t,
+                                                slope_t=seq[hd.prelu_a].weight.detach()) for hd, seq, t in zip(heads, seqs, t1)])
         t2 = [None] * len(heads)
-        for k, hd in enumerate(heads):      # (before the grouped launch: a split-K direct convolution uses the same workspace)
-            if hd["sb"] != 1:
-                t2[k] = ops.conv2d(normed[k], self._pk(f"{hd['name']}.{hd['ib']}", hd["cb"]), hd["cb"].bias.detach(), stride=hd["sb"],
-                                   pad_mode=ops.PAD_REFLECT, in_up=2 if hd["spec"]["up_mid"] else 1)
+        for hd, seq in zip(heads, seqs):    # (before the grouped launch: a split-K direct convolution uses the same workspace)
+            if hd.stride_b != 1:
+                cb = seq[hd.conv_b]
+                t2[hd.index] = ops.conv2d(normed[hd.index], self._pk(f"{hd.name}.{hd.conv_b}", cb), cb.bias.detach(),
+                                          stride=hd.stride_b, pad_mode=ops.PAD_REFLECT, in_up=2 if hd.up_mid else 1)
         # stage 3: second convolutions
-        second = ops.conv3x3_group([conv_item(f"{heads[k]['name']}.{heads[k]['ib']}", heads[k]["cb"], normed[k],
-                                              in_up=2 if heads[k]["spec"]["up_mid"] else 1, defer_reduce=True)
-                                    for k in plain])
-        for j, k in enumerate(plain):
-            t2[k] = second[j]
+        plain = [hd for hd in heads if hd.stride_b == 1]
+        second = ops.conv3x3_group([conv_item(hd, hd.conv_b, normed[hd.index], in_up=2 if hd.up_mid else 1, defer_reduce=True)
+                                    for hd in plain])
+        for hd, t in zip(plain, second):
+            t2[hd.index] = t
         # stage 4: final norms (+ PReLU, x2 upsample, replicated rows) into the trunk's channel slices
-        ops.instnorm_apply_group([dict(x=t2[k], slope_t=hd["seq"][hd["pb"]].weight.detach(), up=2 if hd["spec"]["up_out"] else 1,
-                                       rpad=rpad5 if hd["name"] == "layer5_1" else 0,
-                                       out=trunk[:, hd["i"] * arch.WARP_FEATURE_CH:(hd["i"] + 1) * arch.WARP_FEATURE_CH],
-                                       out_batch_stride=bs) for k, hd in enumerate(heads)])
+        ops.instnorm_apply_group([dict(x=t, slope_t=seq[hd.prelu_b].weight.detach(), up=2 if hd.up_out else 1,
+                                       rpad=rpad5 if hd.name == "layer5_1" else 0,
+                                       out=trunk[:, hd.index * arch.WARP_FEATURE_CH:(hd.index + 1) * arch.WARP_FEATURE_CH],
+                                       out_batch_stride=bs) for hd, seq, t in zip(heads, seqs, t2)])
         return trunk
 
     def _trunk(self, x, saved=None):
@@ -872,23 +852,8 @@ class ColorVidNet(nn.Module):
         return self._cache.get("conv10_ab", out.weight, lambda w: w.detach().reshape(w.shape[0], -1).contiguous())
 
     # ---- decoder blocks: `conv8_1(up(norm(c7_3))) + conv3_3_short(norm(c3_3))` (ColorVidNet.py:124-127; likewise conv9_1,
-    # conv10_1) as ONE launch over the channels of both inputs (ops.conv2d_winograd_dual) when both are Winograd layers
-    def _dual_pairs(self):
-        """consumer key -> the skip-convolution entry whose output it adds (a linear convolution read by nothing else)."""
-        by_dst = {c["dst"]: c for c in arch.CVN_CONVS}
-        uses = {}
-        for c in arch.CVN_CONVS:
-            uses[c["src"]] = uses.get(c["src"], 0) + 1
-            if c["add"] is not None:
-                uses[c["add"]] = uses.get(c["add"], 0) + 1
-        pairs = {}
-        for c in arch.CVN_CONVS:
-            e = by_dst.get(c["add"]) if c["add"] is not None else None
-            if e is not None and e["act"] == "none" and e["add"] is None and uses.get(e["dst"], 0) == 1 and e["dil"] == c["dil"] \
-                    and e["pre"] in (None, "norm") and c["pre"] in ("up", "norm", None):
-                pairs[c["key"]] = e
-        return pairs
-
+    # conv10_1) as ONE launch over the channels of both inputs (ops.conv2d_winograd_dual) when both are Winograd layers.  Which
+    # pairs qualify is arch.CVN_GRAPH.dual; _dual_ok adds what only a call knows (switches, shapes, the engine choice)
     def _dual_pack(self, cA, cB):
         """(concatenated Winograd filters, summed bias) of a fused pair; cached per parameter versions like every pack."""
         mA, mB = self._mod(cA["key"]), self._mod(cB["key"])
@@ -917,9 +882,9 @@ class ColorVidNet(nn.Module):
                 self._ss_weight(c["ss"])
         self._out_weight()
         if ops.conv_algo() != "direct" and ops.dual_conv_enabled():
-            by_key = {c["key"]: c for c in arch.CVN_CONVS}
-            for key, e in self._dual_pairs().items():
-                self._dual_pack(by_key[key], e)
+            G = arch.CVN_GRAPH
+            for key, skip in G.dual.items():
+                self._dual_pack(G.by_key[key], G.by_key[skip])
 
     def forward(self, x):
         """ x: gray image (1 channel), ab(2 channel), ab_err, ba_err"""
@@ -948,25 +913,25 @@ class ColorVidNet(nn.Module):
         the head on dvc_cvn_head_bwd, then CVN_CONVS in reverse — each layer's dZ (ReLU backward, or the InstanceNorm backward
         that gathers the norm's consumers), its weight gradient on dvc_cvn_wgrad, its input gradient on the forward's engines
         with W^T flipped (ops.conv3x3)."""
+        G = arch.CVN_GRAPH
         grads = {}
-        dZ, dW, db = ops.cvn_head_bwd(t["ab"], g_ab, self._out_weight(), t["c10_2"], slope=0.2)
+        dZ, dW, db = ops.cvn_head_bwd(t["ab"], g_ab, self._out_weight(), t[arch.CVN_OUT["src"]], slope=0.2)
         _put_wb(grads, need, arch.CVN_OUT["key"], dW, db)
-        dZ_of = {"c10_2": dZ}
-        adder = {c["add"]: c["dst"] for c in arch.CVN_CONVS if c["add"] is not None}    # skip output -> the block it adds into
-        contrib = {}                                                                        # activation -> {kind: gradient}
+        dZ_of = {arch.CVN_OUT["src"]: dZ}
+        contrib = {}                    # activation -> {kind: gradient}
         dx = None
         for c in reversed(arch.CVN_CONVS):
             key, dst, src, pre = c["key"], c["dst"], c["src"], c["pre"]
             if dst in dZ_of:
                 dZ = dZ_of[dst]
-            elif dst in adder:          # a skip convolution (no activation): the dZ of the block it adds into
-                dZ = dZ_of[adder[dst]]
+            elif dst in G.adder:        # a skip convolution (no activation): the dZ of the block it adds into
+                dZ = dZ_of[G.adder[dst]]
             else:
                 g = contrib.pop(dst)
                 if "raw" in g:
                     dZ = ops.vgg_act_bwd(g["raw"], None, t[dst], out=g["raw"])
                 else:
-                    ss_key = next((e["ss"] for e in arch.CVN_CONVS if e["src"] == dst and e["pre"] == "norm_ss"), None)
+                    ss_key = G.ss_of.get(dst)
                     dZ, dss = ops.cvn_inorm_bwd(t["n:" + dst], t["rstd:" + dst], t[dst], g_full=g.get("full"), g_ss=g.get("ss"),
                                                 ss_w=self._ss_weight(ss_key) if ss_key else None, g_up=g.get("up"))
                     if dss is not None and ss_key + ".weight" in need:
@@ -984,7 +949,7 @@ class ColorVidNet(nn.Module):
                 continue
             wt, packs = self._bwd_filters(key)
             gi = ops.conv3x3(dZ, wt, packs, None, dil=c["dil"], layer="cvn_bwd." + key)
-            kind = {None: "raw", "norm": "full", "norm_ss": "ss", "up": "up"}[pre]
+            kind = G.grad_kind[pre]
             assert kind not in contrib.get(src, {}), (src, kind)
             contrib.setdefault(src, {})[kind] = gi
         return dx, grads
@@ -995,14 +960,10 @@ class ColorVidNet(nn.Module):
         "nss:" + source) and its per-plane 1/sigma in `rstd`.  The split-K reduce is then never deferred into a norm's launch
         (bit-identical either way), so that every activation exists as a tensor."""
         x = x.detach().contiguous().float()
+        G = arch.CVN_GRAPH
         acts = {"x": x}
         normed = {}
         ss_weight = self._ss_weight
-
-        # activations that are normalised for two consumers (skip convolution: plain; next block: * `_ss`
-        # weight, stride 2) get both tensors from one launch
-        both = {c["src"]: c["ss"] for c in arch.CVN_CONVS if c["pre"] == "norm_ss"}
-        both = {k: v for k, v in both.items() if any(c["src"] == k and c["pre"] in ("norm", "up") for c in arch.CVN_CONVS)}
 
         def rstd_buf(src, ss_key=None):
             if saved is None:
@@ -1013,12 +974,15 @@ class ColorVidNet(nn.Module):
             return rstd[src]
 
         def norm_of(src, ss_key=None):
-            """InstanceNorm2d(src) [* the depthwise `_ss` weight, stride 2] as a tensor (ColorVidNet.py:85-94,12)."""
+            """InstanceNorm2d(src) [* the depthwise `_ss` weight, stride 2] as a tensor (ColorVidNet.py:85-94,12).  An
+            activation of G.norm_pair (skip convolution: plain; next block: * `_ss` weight, stride 2) gets both tensors from
+            one launch."""
             k = (src, ss_key)
             if k not in normed:
-                if src in both:
-                    normed[(src, None)], normed[(src, both[src])] = ops.instnorm_apply(
-                        acts[src], eps=1e-5, second=(ss_weight(both[src]), 2), scale_out=rstd_buf(src))
+                pair = G.norm_pair.get(src)
+                if pair is not None:
+                    normed[(src, None)], normed[(src, pair)] = ops.instnorm_apply(
+                        acts[src], eps=1e-5, second=(ss_weight(pair), 2), scale_out=rstd_buf(src))
                 else:
                     normed[k] = ops.instnorm_apply(acts[src], eps=1e-5,
                                                    chan_scale=ss_weight(ss_key) if ss_key else None,
@@ -1029,26 +993,17 @@ class ColorVidNet(nn.Module):
                             saved[("nss:" if k_ else "n:") + src] = v
             return normed[k]
 
-        # activations that are only ever read through an InstanceNorm: normalised right after the convolution that
-        # produces them, which may then leave its split-K partial sums for the InstanceNorm launch to add up
-        norm_uses = {}
-        raw_use = set()
-        for c in arch.CVN_CONVS:
-            if c["pre"] in ("norm", "norm_ss", "up"):
-                norm_uses.setdefault(c["src"], []).append(c["ss"] if c["pre"] == "norm_ss" else None)
-            else:
-                raw_use.add(c["src"])
-            if c["add"] is not None:
-                raw_use.add(c["add"])
-        raw_use.add(arch.CVN_OUT.get("src", "c10_2"))
+        def produced(dst):
+            """Right after `dst` exists: the norms its consumers read (for G.norm_only that launch also adds up the split-K
+            partial sums the convolution left)."""
+            for ss_key in G.norm_variants.get(dst, ()):
+                norm_of(dst, ss_key)
 
         act_map = {"relu": ops.ACT_RELU, "none": ops.ACT_NONE, "leaky": ops.ACT_LEAKY}
-        pairs = self._dual_pairs()
-        deferred = {e["key"] for e in pairs.values()}
         for c in arch.CVN_CONVS:
-            if c["key"] in deferred:
+            if c["key"] in G.skip_keys:
                 continue            # the skip convolution of a decoder block: runs with its consumer below (or just before it)
-            e = pairs.get(c["key"])
+            e = G.by_key.get(G.dual.get(c["key"]))
             if e is not None:
                 srcA = norm_of(c["src"]) if c["pre"] in ("norm", "up") else acts[c["src"]]
                 srcB = norm_of(e["src"]) if e["pre"] == "norm" else acts[e["src"]]
@@ -1060,9 +1015,7 @@ class ColorVidNet(nn.Module):
                                              in_up=2 if cc_["pre"] == "up" else 1, dual=c["key"])
                     acts[c["dst"]] = ops.conv2d_winograd_dual(srcA, srcB, u, b, dil=c["dil"], in_upA=2 if c["pre"] == "up" else 1,
                                                               act=act_map[c["act"]], act_slope=0.2)
-                    if c["dst"] in norm_uses:
-                        for ss_key in dict.fromkeys(norm_uses[c["dst"]]):
-                            norm_of(c["dst"], ss_key)
+                    produced(c["dst"])
                     continue
                 # not both Winograd layers (direct algorithm, tiny maps): the skip convolution as its own launch, then the adder
                 convE = self._mod(e["key"])
@@ -1083,18 +1036,10 @@ class ColorVidNet(nn.Module):
                 kw["residual"] = acts[c["add"]]
             dst = c["dst"]
             acts[dst] = ops.conv3x3(src, conv.weight, _packs(self._cache, c["key"], conv.weight), conv.bias.detach(),
-                                    defer_reduce=dst in norm_uses and dst not in raw_use and saved is None, layer="cvn." + c["key"],
-                                    **kw)
-            if dst in norm_uses:
-                if dst in both:
-                    norm_of(dst)
-                else:
-                    for ss_key in dict.fromkeys(norm_uses[dst]):
-                        norm_of(dst, ss_key)
+                                    defer_reduce=dst in G.norm_only and saved is None, layer="cvn." + c["key"], **kw)
+            produced(dst)
         out = self._mod(arch.CVN_OUT["key"])
         if saved is not None:
-            for c in arch.CVN_CONVS:
-                if c["act"] != "none":
-                    saved[c["dst"]] = acts[c["dst"]]
+            saved.update((a, acts[a]) for a in G.saved_acts)
             saved["x"] = x
-        return ops.conv1x1_small(acts["c10_2"], self._out_weight(), out.bias.detach(), act=ops.ACT_TANH128)
+        return ops.conv1x1_small(acts[arch.CVN_OUT["src"]], self._out_weight(), out.bias.detach(), act=ops.ACT_TANH128)
