@@ -126,6 +126,9 @@ SIGNATURES = {
                                    ctypes.c_float, ctypes.c_float, c_i32, ctypes.c_float, _VP, _VP]),
     "dvc_lwa_bwd": (ctypes.c_int, [_VP, c_i32, c_i32, c_i32, _VP, c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.c_float,
                                    ctypes.c_float, ctypes.c_float, c_i32, ctypes.c_float, _VP, _VP, _VP, _VP, _VP]),
+    "dvc_flow_warp_bwd_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32, c_i32, c_i32]),
+    "dvc_flow_warp_fwd": (ctypes.c_int, [_VP, _VP, c_i32, c_i32, c_i32, c_i32, c_i32, _VP, _VP]),
+    "dvc_flow_warp_bwd": (ctypes.c_int, [_VP, _VP, _VP, c_i32, c_i32, c_i32, c_i32, c_i32, _VP, _VP, _VP, ctypes.c_size_t, _VP]),
     "dvc_vgg_act_bwd": (ctypes.c_int, [_VP, _VP, _VP, c_i64, _VP, _VP]),
     "dvc_vgg_pool_act_bwd": (ctypes.c_int, [_VP, _VP, _VP, _VP, c_i32, c_i32, c_i32, c_i32, _VP, _VP]),
     "dvc_vgg_conv1_bwd": (ctypes.c_int, [_VP, _VP, c_i32, c_i32, c_i32, c_i32, _VP, _VP]),

@@ -520,6 +520,28 @@ int dvc_lwa_bwd(const float* x_lab, int32_t Cx, int32_t Hx, int32_t Wx, const fl
                 const float* G, const float* y, float* d_pred_ab, float* d_guide, dvcStream stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Flow warp (utils/warping.py, WarpingLayer: get_grid + F.grid_sample, bilinear, zeros padding), the temporal-consistency
+ * term's warp, forward and backward — csrc/flow_warp.hip.  x [B][C][H][W], flow [B][2][H][W] (channel 0 = x displacement,
+ * channel 1 = y displacement, in pixels), y [B][C][H][W], all fp32 contiguous.  Per output pixel (y, x) the sample position is
+ *     align_corners = 1:  px = x + u,                         py = y + v
+ *     align_corners = 0:  px = (x + u) W / (W - 1) - 0.5,     py = (y + v) H / (H - 1) - 0.5     (F.grid_sample's default)
+ * and the output is the bilinear mix of the four corners around it, a corner outside the image counting as 0.  Coordinates
+ * and weights are computed in double.  A NaN / inf coordinate gives NaN in every channel of that pixel, adds nothing to dx and
+ * gives a NaN dflow; a finite one of any size is range-checked before it becomes an index.
+ * dvc_flow_warp_bwd: for G [B][C][H][W], dx [B][C][H][W] and dflow [B][2][H][W], each optional (NULL = not wanted, not both).
+ * dflow is a gather.  dx is a scatter done in exact integer arithmetic: per image, contributions are quantised to
+ * 2^(e - 40), 2^e the smallest power of two above max |G| of that image, and added with 64-bit integer atomics, so dx is
+ * bitwise reproducible, does not depend on B, and is within H W 2^-41 max |G| of exact before its one rounding to fp32.
+ * max |G| == 0 gives dx = 0; a NaN / inf in an image's G gives a NaN dx for that image.  workspace (only read when dx is
+ * wanted): dvc_flow_warp_bwd_workspace_bytes(B, C, H, W) bytes, 8-byte aligned, contents arbitrary (it is zeroed on the
+ * stream).  B, C >= 1; H, W >= 2; H W <= 2^22.  Bad arguments are reported before any launch. */
+size_t dvc_flow_warp_bwd_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W);
+int dvc_flow_warp_fwd(const float* x, const float* flow, int32_t B, int32_t C, int32_t H, int32_t W, int32_t align_corners,
+                      float* y, dvcStream stream);
+int dvc_flow_warp_bwd(const float* x, const float* flow, const float* G, int32_t B, int32_t C, int32_t H, int32_t W,
+                      int32_t align_corners, float* dx, float* dflow, void* workspace, size_t workspace_bytes, dvcStream stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Input gradient of VGG19_pytorch (frozen weights) and of tensor_lab2rgb — csrc/vgg_bwd.hip.  The 3x3 convolutions' input
  * gradients run on dvc_conv2d / dvc_conv2d_winograd / dvc_conv2d_ws with the transposed, flipped filters; these are the steps
  * between them.  Masks and routes follow ATen: threshold_backward(grad, relu_out, 0) zeroes the gradient where out <= 0;
