@@ -5,20 +5,19 @@ them: `contextual_forward_loss(predict_relu5_1, B_relu5_1.detach())` on VGG feat
 and of the exemplar (detached).  Same constructor / forward signatures, same per-sample return value [B].
 
     mu = mean_j Y;  Xn, Yn = (. - mu) / (||.||_C + eps)      dvc_cx_prepare
-    S  = Xn^T Yn  in blocks of R rows, the whole batch at once  1x1-convolution engine with per-image filters (ops.conv2d)
+    S  = Xn^T Yn  in blocks of R rows, the whole batch at once  block_products.scores   (vendor GEMM, or the 1x1-conv engine)
     a_i, j*_i, l_i, r_i = max_j A_ij, E_i                     dvc_cx_rows          (A = softmax_j((1 - d / a_i) / h), d = 1 - S)
     column maxima of A over the rows (ContextualLoss only)    dvc_cx_colmax
     loss = -log mean(.)                                       dvc_cx_finish
-backward (w.r.t. X; Y is data, as in train.py): S block recomputed, dS by dvc_cx_ds (+ dvc_cx_rows_tq), d Xn = Yn dS^T on
-the engine, then dvc_cx_normalize_bwd.  Nothing N x N outlives a row block.  Parity: tests/test_gpu_contextual.py against
+backward (w.r.t. X; Y is data, as in train.py): S block recomputed, dS by dvc_cx_ds (+ dvc_cx_rows_tq), d Xn = Yn dS^T
+(block_products.grad_rows), then dvc_cx_normalize_bwd.  Nothing N x N outlives a row block.  Parity: tests/test_gpu_contextual.py against
 float64 autograd through the oracle restatement (oracle/contextual_oracle.py, pinned to the reference module).
 """
-import ctypes
-
 import torch
 import torch.nn as nn
 
 from . import _lib, ops
+from .block_products import block_products
 from .ops import EPS64, _p, _stream
 
 ROW_BLOCK = 2048
@@ -33,17 +32,14 @@ def _row_block(B, Nx, Ny):
 
 
 def _apply(X, Y, h, centering, mode):
-    """The batched launch plan needs 16-byte aligned per-image filters (C * R and Ny * C multiples of 4); odd feature-map
-    sizes take one image per call, as up to r03."""
+    """The engine's batched products need 16-byte aligned per-image filters (block_products: Ny * C a multiple of 4; C * R
+    always is): odd feature-map sizes take one image per call — under either GEMM switch, so that the switch changes how a
+    product is issued and nothing else."""
     B, C = X.shape[0], X.shape[1]
     Ny = Y[0, 0].numel()
     if B > 1 and (Ny * C) % 4 != 0:
         return torch.cat([_ContextualCX.apply(X[b:b + 1], Y[b:b + 1], h, centering, mode) for b in range(B)])
     return _ContextualCX.apply(X, Y, h, centering, mode)
-
-
-def _ip(t):
-    return ctypes.c_void_p(t.data_ptr())
 
 
 class _ContextualCX(torch.autograd.Function):
@@ -72,28 +68,19 @@ class _ContextualCX(torch.autograd.Function):
         loss, gscale = torch.empty(B, **f32), torch.empty(B, **f32)
         R = _row_block(B, Nx, Ny)
         hy, wy = (Y.shape[2], Y.shape[3]) if Y.dim() == 4 else (1, Ny)
-        # r04: the whole batch per launch — S[b] = Xn[b]^T Yn[b] is a 1x1 convolution with PER-IMAGE filters (a batched GEMM,
-        # DvcConvDesc.w_batch_stride) and the row / column kernels take the batch as a grid dimension
-        lib_gemm = ops.gemm_lib()     # r06: S through the vendor's batched GEMM (ops.bmm), no staging copy, no padded rows
-        S = None if lib_gemm else torch.empty((B, R, hy, wy), **f32)
-        blk = None if lib_gemm else torch.zeros((B, C, 1, R), **f32)           # K-major blocks of Xn columns (one buffer for every block)
-        y_img = Yn.view(B, C, hy, wy)
-        S_bs = R * Ny
-        Sbuf = {}
+        # the whole batch per launch: S[b] = Xn[b]^T Yn[b] is a batched product (block_products) and the row / column kernels
+        # take the batch as a grid dimension
+        prod = block_products(Xn, Yn, (hy, wy), R, B)
+        prod.images(slice(0, B))
         for i0 in range(0, Nx, R):
             rows = min(R, Nx - i0)
-            if lib_gemm:
-                S = Sbuf.setdefault(rows, torch.empty((B, rows, Ny), **f32))
-                S_bs = rows * Ny
-                ops.bmm(Xn[:, :, i0:i0 + rows].transpose(1, 2), Yn, out=S)
-            else:
-                _s_block(Xn, y_img, i0, rows, R, S, blk)
+            S, ld = prod.scores(i0, rows)
             sl = slice(i0, i0 + rows)
-            _lib.check(lib.dvc_cx_rows(_p(S), B, S_bs, Nx, rows, Ny, float(h), _p(a[:, sl]), _ip(jstar[:, sl]), _p(l[:, sl]),
+            _lib.check(lib.dvc_cx_rows(_p(S), B, ld * Ny, Nx, rows, Ny, float(h), _p(a[:, sl]), _p(jstar[:, sl]), _p(l[:, sl]),
                                        _p(r[:, sl]), _p(e[:, sl]), st), "dvc_cx_rows")
             if mode == 1:
-                _lib.check(lib.dvc_cx_colmax(_p(S), B, S_bs, Nx, _p(a[:, sl]), _p(l[:, sl]), rows, Ny, i0, float(h), _p(cmax),
-                                             _ip(cargi), st), "dvc_cx_colmax")
+                _lib.check(lib.dvc_cx_colmax(_p(S), B, ld * Ny, Nx, _p(a[:, sl]), _p(l[:, sl]), rows, Ny, i0, float(h), _p(cmax),
+                                             _p(cargi), st), "dvc_cx_colmax")
         v, n = (r, Nx) if mode == 0 else (cmax, Ny)
         _lib.check(lib.dvc_cx_finish(_p(v), B, n, _p(loss), _p(gscale), st), "dvc_cx_finish")
         saved = [Xn, Yn, normX, a, l, r, e, jstar, gscale] + ([cargi] if mode == 1 else [])
@@ -110,72 +97,29 @@ class _ContextualCX(torch.autograd.Function):
         cargi = saved[9] if mode == 1 else None
         B, C, Nx = Xn.shape
         Ny = Yn.shape[2]
-        dev = Xn.device
-        f32 = dict(device=dev, dtype=torch.float32)
         st = _stream()
         # the incoming per-sample gradient is folded into the per-sample scale ON THE DEVICE (dvc_cx_ds multiplies the two):
         # no host read-back, the backward pass only enqueues
         gs = (gscale * gout.detach().to(gscale.dtype)).contiguous()
         R = _row_block(B, Nx, Ny)
-        lib_gemm = ops.gemm_lib()     # r06: both products through the vendor's batched GEMM (ops.bmm); dS row-major only
-        tt, qq = (torch.empty((B, R), **f32), torch.empty((B, R), **f32)) if mode == 1 else (None, None)
+        tt, qq = (Xn.new_empty((B, R)), Xn.new_empty((B, R))) if mode == 1 else (None, None)
         dXn = torch.empty_like(Xn)
-        y_img = Yn.view(B, C, hy, wy)
-        if lib_gemm:
-            bufs = {}
-            for i0 in range(0, Nx, R):
-                rows = min(R, Nx - i0)
-                if rows not in bufs:
-                    bufs[rows] = (torch.empty((B, rows, Ny), **f32), torch.empty((B, rows, Ny), **f32), torch.empty((B, C, rows), **f32))
-                S, dS, dxb = bufs[rows]
-                S_bs = rows * Ny
-                ops.bmm(Xn[:, :, i0:i0 + rows].transpose(1, 2), Yn, out=S)
-                sl = slice(i0, i0 + rows)
-                if mode == 1:
-                    _lib.check(lib.dvc_cx_rows_tq(_p(S), B, S_bs, Nx, R, _p(a[:, sl]), _p(l[:, sl]), _ip(cargi), rows, Ny, i0, h, _p(tt),
-                                                  _p(qq), st), "dvc_cx_rows_tq")
-                _lib.check(lib.dvc_cx_ds(_p(S), B, S_bs, Nx, R, _p(a[:, sl]), _p(l[:, sl]), _p(r[:, sl]), _p(e[:, sl]), _ip(jstar[:, sl]),
-                                         None if cargi is None else _ip(cargi), _p(tt), _p(qq), _p(gs), 1.0, mode, rows, Ny, i0, rows, h,
-                                         _p(dS), None, st), "dvc_cx_ds")
-                # d Xn[b, c, i0 + i] = sum_j Yn[b, c, j] dS[b, i, j]   (one block for all rows: straight into dXn, no copy)
-                if rows == Nx:
-                    ops.bmm(Yn, dS.transpose(1, 2), out=dXn)
-                else:
-                    ops.bmm(Yn, dS.transpose(1, 2), out=dxb)
-                    dXn[:, :, i0:i0 + rows] = dxb
-            dX = torch.empty_like(Xn)
-            _lib.check(lib.dvc_cx_normalize_bwd(_p(Xn), _p(normX), _p(dXn), B, C, Nx, float(EPS64), _p(dX), st), "dvc_cx_normalize_bwd")
-            return dX.view(xshape), None, None, None, None
-        S = torch.empty((B, R, hy, wy), **f32)
-        blk = torch.zeros((B, C, 1, R), **f32)
-        dST = torch.empty((B, Ny, R // 32, 32), **f32)                       # [Ny][R] per image, as an image of R "pixels"
-        y_t = Yn.transpose(1, 2).contiguous().view(B, Ny, 1, C)              # K-major per-image filters of d Xn = Yn dS^T
-        S_bs = R * Ny
+        prod = block_products(Xn, Yn, (hy, wy), R, B, want_rows=True)
+        prod.images(slice(0, B))
         for i0 in range(0, Nx, R):
             rows = min(R, Nx - i0)
-            _s_block(Xn, y_img, i0, rows, R, S, blk)
+            S, ld = prod.scores(i0, rows)
+            dS, dST = prod.ds_targets()
             sl = slice(i0, i0 + rows)
             if mode == 1:
-                _lib.check(lib.dvc_cx_rows_tq(_p(S), B, S_bs, Nx, R, _p(a[:, sl]), _p(l[:, sl]), _ip(cargi), rows, Ny, i0, h, _p(tt),
+                _lib.check(lib.dvc_cx_rows_tq(_p(S), B, ld * Ny, Nx, R, _p(a[:, sl]), _p(l[:, sl]), _p(cargi), rows, Ny, i0, h, _p(tt),
                                               _p(qq), st), "dvc_cx_rows_tq")
-            _lib.check(lib.dvc_cx_ds(_p(S), B, S_bs, Nx, R, _p(a[:, sl]), _p(l[:, sl]), _p(r[:, sl]), _p(e[:, sl]), _ip(jstar[:, sl]),
-                                     None if cargi is None else _ip(cargi), _p(tt), _p(qq), _p(gs), 1.0, mode, rows, Ny, i0, R, h,
-                                     None, _p(dST), st), "dvc_cx_ds")
-            dxb = ops.conv2d(dST, y_t, None, ksize=1, pad=0)                  # [B, C, R/32, 32]
-            dXn[:, :, i0:i0 + rows] = dxb.view(B, C, R)[:, :, :rows]
+            _lib.check(lib.dvc_cx_ds(_p(S), B, ld * Ny, Nx, R, _p(a[:, sl]), _p(l[:, sl]), _p(r[:, sl]), _p(e[:, sl]), _p(jstar[:, sl]),
+                                     _p(cargi), _p(tt), _p(qq), _p(gs), 1.0, mode, rows, Ny, i0, ld, h, _p(dS), _p(dST), st), "dvc_cx_ds")
+            prod.grad_rows(dXn)             # d Xn[b, c, i0 + i] = sum_j Yn[b, c, j] dS[b, i, j]
         dX = torch.empty_like(Xn)
         _lib.check(lib.dvc_cx_normalize_bwd(_p(Xn), _p(normX), _p(dXn), B, C, Nx, float(EPS64), _p(dX), st), "dvc_cx_normalize_bwd")
         return dX.view(xshape), None, None, None, None
-
-
-def _s_block(Xn, y_img, i0, rows, R, S, blk):
-    """S[b, i, :] = sum_c Xn[b, c, i0 + i] Yn[b, c, :] for a block of R rows (zero rows beyond `rows`) of every image of the batch:
-    ONE launch of the 1x1-conv engine with per-image filters.  `blk` [B, C, 1, R]: the caller's staging buffer for the blocks'
-    columns (stream-ordered reuse, no allocation per block)."""
-    if rows < R:
-        blk[..., rows:].zero_()
-    blk[:, :, 0, :rows].copy_(Xn[:, :, i0:i0 + rows])
-    ops.conv2d(y_img, blk, None, ksize=1, pad=0, out=S)
 
 
 def _check(X_features, Y_features):

@@ -1296,6 +1296,7 @@ def corr_fwd_bf16(theta, phi, blab, temperature, h, w, want_small=False, want_ar
 # 103-121 TFLOP/s on the MI355X where this library's 1x1-convolution engine reaches 77-81 (tools/gemm_lib_probe.py; the engine
 # keeps the better rounding: blocked sums, 2e-7 against 9e-7 of the result's scale — both far inside the tolerances of
 # tests/test_gpu_corr_backward.py).  DVC_GEMM_LIB=0 / set_gemm_lib(False) keeps every product on the engine.
+# dvc_amd/block_products.py is the one caller: it issues a row block's products through `bmm` or through `conv2d`, by gemm_lib().
 def bmm(a, b, out=None, accumulate=False):
     """out = a @ b (or out += a @ b) for batched fp32 matrices [B, M, K] x [B, K, N] through the vendor GEMM; `a` / `b` may be
     transposed or column-sliced VIEWS (the library takes leading dimensions).  Plain fp32: TF32-like modes are refused."""

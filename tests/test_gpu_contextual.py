@@ -1,7 +1,9 @@
 """GPU parity of the HIP contextual losses (dvc_amd.contextual) against the oracle restatement of
 /root/reference/models/ContextualLoss.py:29-126 — values against the reference fixtures and the float64 truth, gradients
 w.r.t. X against float64 autograd, at the sizes train.py:649-668 uses (relu5_1 13x24 and relu4_1 27x48 at 216x384; the
-downsampled relu3_1 is 27x48 too) and at a size with several row blocks."""
+downsampled relu3_1 is 27x48 too): every one of them a single row block (ROW_BLOCK = 2048 against at most 27 x 48 = 1296 rows).
+Several row blocks and a ragged last block run in `..._over_several_row_blocks`, on small maps with ROW_BLOCK lowered to 64;
+the one-image-per-call fallback in `..._one_image_per_call`."""
 import glob
 import os
 
@@ -53,6 +55,30 @@ def gemm_mode(request):
 @pytest.mark.parametrize("C,H,W,B,h,centre", [(512, 13, 24, 2, 0.1, True), (512, 27, 48, 1, 0.1, True), (256, 27, 48, 2, 0.1, True),
                                               (64, 24, 40, 1, 0.2, False), (128, 7, 9, 3, 0.1, True)])
 def test_contextual_loss_vs_float64_autograd(C, H, W, B, h, centre, gemm_mode):
+    _check_vs_float64_autograd(C, H, W, B, h, centre)
+
+
+@pytest.mark.parametrize("C,H,W,B,h,centre", [(64, 10, 15, 2, 0.1, True), (64, 10, 15, 2, 0.2, False), (64, 9, 14, 3, 0.1, True)])
+def test_contextual_loss_over_several_row_blocks(C, H, W, B, h, centre, gemm_mode, monkeypatch):
+    """ROW_BLOCK = 64 (`_row_block` reads the global per call): 150 rows are blocks of 64 / 64 / 22 and 126 rows 64 / 62 — the
+    running column maximum across blocks, the zero rows behind a ragged last block and the staged copy of d Xn.  Same inputs,
+    oracle and tolerances as the single-block test."""
+    from dvc_amd import contextual
+    monkeypatch.setattr(contextual, "ROW_BLOCK", 64)
+    _check_vs_float64_autograd(C, H, W, B, h, centre)
+
+
+def test_contextual_loss_one_image_per_call(monkeypatch):
+    """C = 66 on 7 x 9: Ny * C = 4158 is no multiple of 4 and the batch of 2 takes one image per call.  Vendor GEMM only: the
+    engine refuses the shape whatever the batch (`dvc_conv2d: Cout must be a multiple of 4 (got 66)` in d Xn = Yn dS^T), so
+    with DVC_GEMM_LIB=0 an unaligned Ny * C, which needs C % 4 != 0, has never worked."""
+    from dvc_amd import contextual, ops
+    monkeypatch.setattr(contextual, "ROW_BLOCK", 64)
+    monkeypatch.setattr(ops, "_gemm_lib", True)
+    _check_vs_float64_autograd(66, 7, 9, 2, 0.1, True)
+
+
+def _check_vs_float64_autograd(C, H, W, B, h, centre):
     X, Y = O.synth_features(1000 + C + H, B, C, H, W)
     gout = torch.linspace(0.5, 1.5, B)
     for tag, (mod, fn) in _mods().items():

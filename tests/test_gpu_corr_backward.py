@@ -66,6 +66,33 @@ def test_fused_correlation_backward_vs_oracle_autograd(h, w, B, T, gemm_mode):
     assert (thd2.grad - expect).abs().max().item() < 1e-5
 
 
+@pytest.mark.parametrize("h,w,B,T,block_bytes", [(12, 20, 2, 0.01, None), (12, 20, 2, 0.01, 4 * 64 * 240), (9, 7, 2, 0.05, None)])
+def test_fused_correlation_backward_over_several_row_blocks(h, w, B, T, block_bytes, gemm_mode, monkeypatch):
+    """ROW_BLOCK = 64: 240 rows are blocks of 64 x 3 + 48 (d phi accumulates over four blocks, the last one ragged), 63 rows one
+    ragged block; BLOCK_BYTES = one [1, 64, 240] fp32 buffer makes `chunk` 1, so the image loop runs twice.  Same oracle and
+    tolerances as the single-block test."""
+    from dvc_amd import corr_autograd, ops
+    from oracle import dvc_oracle as O
+    monkeypatch.setattr(corr_autograd, "ROW_BLOCK", 64)
+    if block_bytes is not None:
+        monkeypatch.setattr(corr_autograd, "BLOCK_BYTES", block_bytes)
+    th, ph, lab, gy, gs = _inputs(B, h, w, 100 * h + w)
+    th64, ph64 = th.double().requires_grad_(True), ph.double().requires_grad_(True)
+    y64, sim64, _ = O.correlate(th64, ph64, lab.double(), T)
+    ((y64 * gy.double()).sum() + (sim64 * gs.double()).sum()).backward()
+    thd, phd = th.cuda().requires_grad_(True), ph.cuda().requires_grad_(True)
+    blab = ops.avgpool4x4(lab.cuda()).view(B, 3, -1)
+    y, sim, _ = corr_autograd.fused_correlation(thd, phd, blab, T, h, w)
+    ((y * gy.cuda()).sum() + (sim * gs.cuda()).sum()).backward()
+    torch.cuda.synchronize()
+    assert (sim.detach().cpu().double() - sim64.detach()).abs().max().item() < 2e-6
+    for name, got, ref in (("theta", thd.grad, th64.grad), ("phi", phd.grad, ph64.grad)):
+        err = (got.cpu().double() - ref).abs().max().item()
+        scale = ref.abs().max().item()
+        print(f"corr backward, 64-row blocks, {h}x{w} B={B} T={T} BLOCK_BYTES={block_bytes}: d{name} max err {err:.3e} (max |grad| {scale:.3e})")
+        assert err <= 2e-3 * scale, (name, err, scale)
+
+
 @pytest.mark.parametrize("h,w,B,T,scale", [(12, 20, 2, 0.01, 1e-4), (10, 16, 1, 0.01, 0.5), (12, 20, 1, 0.005, 3.0), (27, 48, 1, 0.01, 0.5)])
 def test_fused_correlation_backward_with_wta_scale(h, w, B, T, scale, gemm_mode):
     """WTA_scale (NonlocalNet.py:288-327, `WTA_scale_weight != 1`), differentiated (r05): float64 autograd through
@@ -131,7 +158,7 @@ def _oracle_grads_row_chunked(th, ph, lab, gy, gs, T, rows=1024):
 @pytest.mark.parametrize("h,w,B,T,autotune", [(54, 96, 2, 0.01, False), (27, 48, 2, 0.01, True), (12, 20, 1, 1e-7, False)])
 def test_fused_correlation_backward_at_the_training_size(h, w, B, T, autotune, gemm_mode):
     """The size the training caller runs (train.py:44,402-427: 216x384 crops -> 54 x 96 = 5184 positions, T = 0.01), B = 2:
-    11 row blocks of 512 per image (the last one 64 rows) against the row-chunked float64 autograd oracle.
+    row blocks of 2048 / 2048 / 1088 per image against the row-chunked float64 autograd oracle.
     `autotune=True` repeats a case with ops.set_autotune(True): the d_phi accumulation `conv2d(dS, ..., residual=out, out=out)`
     aliases its skip input with its output, and the tuner's timing launches must not add into the caller's tensor.
     T = 1e-7: the backward softmax is evaluated around the row maximum of the RECOMPUTED block (another summation order than
