@@ -129,6 +129,11 @@ SIGNATURES = {
     "dvc_flow_warp_bwd_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32, c_i32, c_i32]),
     "dvc_flow_warp_fwd": (ctypes.c_int, [_VP, _VP, c_i32, c_i32, c_i32, c_i32, c_i32, _VP, _VP]),
     "dvc_flow_warp_bwd": (ctypes.c_int, [_VP, _VP, _VP, c_i32, c_i32, c_i32, c_i32, c_i32, _VP, _VP, _VP, ctypes.c_size_t, _VP]),
+    "dvc_bgemm_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32, c_i32, c_i32]),
+    "dvc_bgemm": (ctypes.c_int, [_VP, _VP, _VP, c_i32, c_i32, c_i32, c_i32, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64,
+                                 c_i32, _VP]),
+    "dvc_bgemm_splitk": (ctypes.c_int, [_VP, _VP, _VP, c_i32, c_i32, c_i32, c_i32, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64,
+                                        c_i64, c_i32, _VP, ctypes.c_size_t, _VP]),
     "dvc_vgg_act_bwd": (ctypes.c_int, [_VP, _VP, _VP, c_i64, _VP, _VP]),
     "dvc_vgg_pool_act_bwd": (ctypes.c_int, [_VP, _VP, _VP, _VP, c_i32, c_i32, c_i32, c_i32, _VP, _VP]),
     "dvc_vgg_conv1_bwd": (ctypes.c_int, [_VP, _VP, c_i32, c_i32, c_i32, c_i32, _VP, _VP]),

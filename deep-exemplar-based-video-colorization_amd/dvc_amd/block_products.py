@@ -8,25 +8,57 @@ block of R rows of the "rows" operand L [B, C, Nl] against the "columns" operand
     d M += L_blk dS                grad_cols_accumulate()      (the correlation only)
     d L_blk = M dS^T               grad_rows()
 
-`block_products(...)` picks the implementation once per autograd call by ops.gemm_lib():
+`block_products(...)` picks the implementation once per autograd call: by backend() when one was selected (set_backend /
+use_backend: "vendor", "engine" or "native"), else, as ever, by ops.gemm_lib():
   * vendor (the default): ops.bmm on views — no staging copies, no padded last block, dS row-major only; buffers per
     (images, rows), so a ragged last block has its own;
+  * native: the same views through ops.bgemm, this library's own strided fp32 MFMA GEMM (csrc/bgemm.hip) — no vendor library,
+    any C; selected by name only;
   * engine (DVC_GEMM_LIB=0): ops.conv2d with per-image filters, ksize 1, on buffers of R rows allocated once per call.  The
     block's columns of L are staged K-major (and row-major for d M) with zero rows behind a ragged block, S and dS are
     [nb, R, hm, wm] "images", the caller's kernel also writes dS^T as [nb, Nm, R/32, 32] (an image of R "pixels"), and M^T is
     copied once per image slice.  Per-image filter slices must be 16-byte aligned, else `chunk` becomes 1.
 Use: images(sl_b) once per image slice; per block scores(i0, rows) first — the other three refer to that block.
 """
+import contextlib
+
 import torch
 
 from . import ops
+
+_BACKENDS = (None, "vendor", "engine", "native")
+_backend = None
+
+
+def backend():
+    """The selected backend: "vendor", "engine", "native", or None = ops.gemm_lib() decides between vendor and engine."""
+    return _backend
+
+
+def set_backend(name):
+    global _backend
+    if name not in _BACKENDS:
+        raise ValueError(f"dvc_amd.block_products: unknown backend {name!r}; one of {_BACKENDS}")
+    _backend = name
+
+
+@contextlib.contextmanager
+def use_backend(name):
+    """`with use_backend("native"): ...` — the selection inside the block, the earlier one after it (also on an exception)."""
+    prev = backend()
+    set_backend(name)
+    try:
+        yield
+    finally:
+        set_backend(prev)
 
 
 def block_products(L, M, map_hw, R, chunk, want_rows=False, want_cols=False):
     """L [B, C, Nl], M [B, C, Nm] with Nm = hm * wm, map_hw = (hm, wm); R: rows per block (a multiple of 64); chunk: the most
     images the caller allows per slice (`.chunk` afterwards: what the backend takes); want_rows / want_cols: whether grad_rows /
     grad_cols_accumulate will be called."""
-    return (_Vendor if ops.gemm_lib() else _Engine)(L, M, map_hw, R, chunk, want_rows, want_cols)
+    name = backend() or ("vendor" if ops.gemm_lib() else "engine")
+    return {"vendor": _Vendor, "engine": _Engine, "native": _Native}[name](L, M, map_hw, R, chunk, want_rows, want_cols)
 
 
 class _Products:
@@ -46,7 +78,10 @@ class _Products:
         return self.dS, self.dST
 
 
-class _Vendor(_Products):
+class _Views(_Products):
+    """The products on views of L, M and dS; `product` is ops.bmm (_Vendor) or ops.bgemm (_Native)."""
+    product = None
+
     def _alloc(self, C, Nm):
         return {}
 
@@ -60,19 +95,27 @@ class _Vendor(_Products):
                                      torch.empty((nb, C, rows), **self.f32) if self.want_rows else None)
         self.S, self.dS, self.staged = self.bufs[(nb, rows)]
         self.blk = self.L[self.sl_b, :, i0:i0 + rows]                    # [nb, C, rows] view
-        ops.bmm(self.blk.transpose(1, 2), self.M[self.sl_b], out=self.S)
+        self.product(self.blk.transpose(1, 2), self.M[self.sl_b], out=self.S)
         return self.S, rows
 
     def grad_cols_accumulate(self, out):
         """out[sl_b, c, j] += sum_i L[b, c, i0 + i] dS[b, i, j]"""
-        ops.bmm(self.blk, self.dS, out=out[self.sl_b], accumulate=True)
+        self.product(self.blk, self.dS, out=out[self.sl_b], accumulate=True)
 
     def grad_rows(self, out):
         """out[sl_b, c, i0 + i] = sum_j M[b, c, j] dS[b, i, j]   (a block that is all of `out`: straight into it, no copy)"""
         whole = (self.nb, self.rows) == (out.shape[0], out.shape[2])
-        ops.bmm(self.M[self.sl_b], self.dS.transpose(1, 2), out=out if whole else self.staged)
+        self.product(self.M[self.sl_b], self.dS.transpose(1, 2), out=out if whole else self.staged)
         if not whole:
             out[self.sl_b, :, self.i0:self.i0 + self.rows] = self.staged
+
+
+class _Vendor(_Views):
+    product = staticmethod(ops.bmm)
+
+
+class _Native(_Views):
+    product = staticmethod(ops.bgemm)
 
 
 class _Engine(_Products):

@@ -5,7 +5,7 @@ them: `contextual_forward_loss(predict_relu5_1, B_relu5_1.detach())` on VGG feat
 and of the exemplar (detached).  Same constructor / forward signatures, same per-sample return value [B].
 
     mu = mean_j Y;  Xn, Yn = (. - mu) / (||.||_C + eps)      dvc_cx_prepare
-    S  = Xn^T Yn  in blocks of R rows, the whole batch at once  block_products.scores   (vendor GEMM, or the 1x1-conv engine)
+    S  = Xn^T Yn  in blocks of R rows, the whole batch at once  block_products.scores   (vendor GEMM, 1x1-conv engine or ops.bgemm)
     a_i, j*_i, l_i, r_i = max_j A_ij, E_i                     dvc_cx_rows          (A = softmax_j((1 - d / a_i) / h), d = 1 - S)
     column maxima of A over the rows (ContextualLoss only)    dvc_cx_colmax
     loss = -log mean(.)                                       dvc_cx_finish

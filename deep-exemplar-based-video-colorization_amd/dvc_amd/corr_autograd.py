@@ -11,7 +11,8 @@ keeping the P x P matrices autograd would have saved (4 x 107 MB per image at 21
         d phi += theta_blk dS ;  d theta_blk = phi dS^T            batched GEMMs
 
 The three products are plain fp32 GEMMs, issued by dvc_amd.block_products: the vendor's batched GEMM by default (ops.bmm), this
-library's 1x1-convolution engine with per-image filters under DVC_GEMM_LIB=0.
+library's 1x1-convolution engine with per-image filters under DVC_GEMM_LIB=0, this library's own strided fp32 GEMM (ops.bgemm)
+under block_products.set_backend("native").
 
 Gradients flow to theta and phi (the centred, normalised projections); the pooled exemplar colours are data (no
 gradient).  r05: the WTA re-weighting (`WTA_scale_weight != 1`, NonlocalNet.py:288-327; dead in both reference drivers) is

@@ -1296,7 +1296,8 @@ def corr_fwd_bf16(theta, phi, blab, temperature, h, w, want_small=False, want_ar
 # 103-121 TFLOP/s on the MI355X where this library's 1x1-convolution engine reaches 77-81 (tools/gemm_lib_probe.py; the engine
 # keeps the better rounding: blocked sums, 2e-7 against 9e-7 of the result's scale — both far inside the tolerances of
 # tests/test_gpu_corr_backward.py).  DVC_GEMM_LIB=0 / set_gemm_lib(False) keeps every product on the engine.
-# dvc_amd/block_products.py is the one caller: it issues a row block's products through `bmm` or through `conv2d`, by gemm_lib().
+# dvc_amd/block_products.py is the one caller: it issues a row block's products through `bmm` or through `conv2d`, by gemm_lib(),
+# or — block_products.set_backend("native") — through `bgemm`, this library's own strided GEMM, which needs neither.
 def bmm(a, b, out=None, accumulate=False):
     """out = a @ b (or out += a @ b) for batched fp32 matrices [B, M, K] x [B, K, N] through the vendor GEMM; `a` / `b` may be
     transposed or column-sliced VIEWS (the library takes leading dimensions).  Plain fp32: TF32-like modes are refused."""
@@ -1311,6 +1312,55 @@ def bmm(a, b, out=None, accumulate=False):
             raise RuntimeError("dvc_amd: accumulate needs `out`")
         return torch.baddbmm(out, a, b, out=out)
     return torch.bmm(a, b, out=out) if out is not None else torch.bmm(a, b)
+
+
+def _inner_strides(t, name):
+    """(batch, first, second) strides of a [B, X, Y] view for dvc_bgemm; a dimension of size 1 never decides the layout."""
+    sb, s1, s2 = t.stride()
+    if t.shape[1] == 1 and s2 != 1:
+        s1 = 1
+    if t.shape[2] == 1 and s1 != 1:
+        s2 = 1
+    if (s1 != 1 and s2 != 1) or min(sb, s1, s2) < 0:
+        raise RuntimeError(f"dvc_amd: `{name}` needs one inner stride of 1 (a transposed or column-sliced view of a contiguous "
+                           f"tensor); got strides {tuple(t.stride())}")
+    return (0 if t.shape[0] == 1 else sb), s1, s2
+
+
+def bgemm(a, b, out=None, accumulate=False):
+    """out = a @ b (or out += a @ b) for batched fp32 matrices [B, M, K] x [B, K, N] on this library's own GEMM (dvc_bgemm_splitk,
+    csrc/bgemm.hip: exact-fp32 MFMA, bit-reproducible, an image's bits independent of the batch).  Same contract as `bmm`: `a` /
+    `b` may be transposed or column-sliced VIEWS, `out` a view with unit inner stride; the strides go to the kernel, nothing is
+    copied.  Nothing of torch's is used, so its TF32 setting is not looked at.  Sizes with few output tiles are split over K:
+    their partial sums live in the per-stream scratch cache (`_workspace`, tag "bgemm": slices x B x M x N floats, grow-only — a
+    d L = M dS^T of 16 images at R = 2048 keeps 268 MB for the life of the process)."""
+    for t, name in ((a, "a"), (b, "b"), (out, "out")):
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"dvc_amd: `{name}` must be a ROCm device tensor; the HIP path has no CPU fallback")
+        if t.dtype != torch.float32 or t.dim() != 3:
+            raise RuntimeError(f"dvc_amd: `{name}` must be a float32 ROCm tensor [B, M, K]")
+        if t.device.index != _current_device():
+            raise RuntimeError(f"dvc_amd: `{name}` lives on {t.device} but the current device is cuda:{_current_device()}")
+    (B, M, K), N = a.shape, b.shape[2]
+    if b.shape[0] != B or b.shape[1] != K or min(B, M, N, K) < 1:
+        raise RuntimeError(f"dvc_amd: bgemm shapes do not match: a {tuple(a.shape)}, b {tuple(b.shape)}")
+    if out is None:
+        if accumulate:
+            raise RuntimeError("dvc_amd: accumulate needs `out`")
+        out = torch.empty((B, M, N), device=a.device, dtype=torch.float32)
+    ldc = out.stride(1) if M > 1 else max(out.stride(1), N)
+    if tuple(out.shape) != (B, M, N) or (out.stride(2) != 1 and N > 1) or ldc < N or (B > 1 and out.stride(0) < 0):
+        raise RuntimeError(f"dvc_amd: `out` must be [B, M, N] = {(B, M, N)} with unit inner stride and rows at least N apart; "
+                           f"got shape {tuple(out.shape)}, strides {tuple(out.stride())}")
+    a_s, b_s = _inner_strides(a, "a"), _inner_strides(b, "b")
+    lib = _lib.load()
+    nbytes = lib.dvc_bgemm_workspace_bytes(B, M, N, K)
+    ws = _workspace(a.device, nbytes, "bgemm") if nbytes else None
+    _lib.check(lib.dvc_bgemm_splitk(_p(a), _p(b), _p(out), B, M, N, K, *a_s, *b_s, 0 if B == 1 else out.stride(0), ldc,
+                                    int(bool(accumulate)), _p(ws), nbytes, _stream()), "dvc_bgemm_splitk")
+    return out
 
 
 def lab2rgb_bwd(lab, grad_rgb, l_offset=0.0):

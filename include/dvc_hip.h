@@ -542,6 +542,29 @@ int dvc_flow_warp_bwd(const float* x, const float* flow, const float* G, int32_t
                       int32_t align_corners, float* dx, float* dflow, void* workspace, size_t workspace_bytes, dvcStream stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Batched fp32 GEMM on strided views — csrc/bgemm.hip: the products of the training side's row-block loops
+ * (dvc_amd/block_products.py) without a vendor library.
+ *     C[b][m][n] (+)= sum_k A[b][m][k] B[b][k][n],   b < batch, m < M, n < N, k < K   (all >= 1; M = 1 and K = 1 are legal)
+ * Strides are in elements: A[b][m][k] at A + b a_sb + m a_sm + k a_sk, B[b][k][n] at B + b b_sb + k b_sk + n b_sn, C[b][m][n] at
+ * C + b c_sb + m ldc + n with ldc >= N.  One of (a_sm, a_sk) and one of (b_sk, b_sn) must be 1: transposed and column-sliced
+ * views of contiguous tensors.  No alignment beyond 4 bytes is needed (16-byte reads are used where pointer and strides allow).
+ * accumulate = 0: C is written and never read (a NaN in the old C does not leak, elements between N and ldc are untouched);
+ * accumulate = 1: C += A B.  Products and sums are exact-fp32 MFMA (v_mfma_f32_32x32x2_f32), each element a k-ordered fma
+ * chain; no atomics: results are bit-identical from run to run and an image's bits do not depend on the batch around it.
+ * dvc_bgemm never splits K.  dvc_bgemm_splitk cuts K into slices when the output has too few 128 x 128 tiles to fill the chip
+ * (the slice count depends on M, N, K only): partial sums go to `workspace` (dvc_bgemm_workspace_bytes(batch, M, N, K) bytes,
+ * 0 = these sizes are not split and workspace may be NULL; contents arbitrary) and a second launch adds them in slice order.
+ * Its bits differ from dvc_bgemm's where it splits, and are as reproducible.  Bad arguments (a null pointer, a non-positive
+ * size, ldc < N, neither inner stride 1, a negative stride, a missing or short workspace) are reported before any launch. */
+size_t dvc_bgemm_workspace_bytes(int32_t batch, int32_t M, int32_t N, int32_t K);
+int dvc_bgemm(const float* A, const float* B, float* C, int32_t batch, int32_t M, int32_t N, int32_t K, int64_t a_sb, int64_t a_sm,
+              int64_t a_sk, int64_t b_sb, int64_t b_sk, int64_t b_sn, int64_t c_sb, int64_t ldc, int32_t accumulate,
+              dvcStream stream);
+int dvc_bgemm_splitk(const float* A, const float* B, float* C, int32_t batch, int32_t M, int32_t N, int32_t K, int64_t a_sb,
+                     int64_t a_sm, int64_t a_sk, int64_t b_sb, int64_t b_sk, int64_t b_sn, int64_t c_sb, int64_t ldc,
+                     int32_t accumulate, void* workspace, size_t workspace_bytes, dvcStream stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Input gradient of VGG19_pytorch (frozen weights) and of tensor_lab2rgb — csrc/vgg_bwd.hip.  The 3x3 convolutions' input
  * gradients run on dvc_conv2d / dvc_conv2d_winograd / dvc_conv2d_ws with the transposed, flipped filters; these are the steps
  * between them.  Masks and routes follow ATen: threshold_backward(grad, relu_out, 0) zeroes the gradient where out <= 0;
