@@ -1,8 +1,9 @@
-// What the backward files (cvn_bwd.hip, warp_bwd.hip) share: the fixed-order slot sum, the fixed-order block sum, and the frame
-// of the two fp32-MFMA weight-gradient kernels (slot heuristic, chunk range, epilogue stores, host-side checks).  The library is
-// built with -fno-gpu-rdc: everything here is in an anonymous namespace and each including file gets its own instance.
+// What the backward files (cvn_bwd.hip, warp_bwd.hip) share: the fixed-order slot sum, the fixed-order block sum (reduce.h), and
+// the frame of the two fp32-MFMA weight-gradient kernels (slot heuristic, chunk range, epilogue stores, host-side checks).  The
+// library is built with -fno-gpu-rdc: everything here is in an anonymous namespace and each including file gets its own instance.
 #pragma once
 #include "common.h"
+#include "reduce.h"
 
 namespace {
 
@@ -23,22 +24,6 @@ static int launch_sum_slots(const float* part, int S, long ld, long n, float* ou
     const long blocks = cdivl(n, 256);
     hipLaunchKernelGGL(sum_slots_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st, part, S, ld, n, out);
     return 0;
-}
-
-// ------------------------------------------------------------------------------------------------ fixed-order block sum
-// Sum of v over the NT threads of a workgroup, the same value in every thread: butterfly inside each wave, then the waves' sums
-// in wave order.  red: NT / 64 elements of LDS; two calls may share it (the leading barrier protects the previous call's reads).
-template <typename T, int NT>
-__device__ __forceinline__ T block_sum(T v, T* red) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    __syncthreads();
-    if (lane == 0) red[wave] = v;
-    __syncthreads();
-    T s = red[0];
-    for (int k = 1; k < NT / 64; ++k) s += red[k];
-    return s;
 }
 
 // ------------------------------------------------------------------------------------------------ weight-gradient frame

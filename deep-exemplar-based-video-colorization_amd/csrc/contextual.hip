@@ -7,92 +7,17 @@
 //     loss = -log CX
 // The GEMMs (S and the two gradient products) run on the 1x1-convolution engine from the host side
 // (dvc_amd/contextual.py), in blocks of R rows of S; this file holds the bandwidth-bound pieces in between, forward
-// and backward.  Feature maps on this path have N <= 1296 positions (27x48), so a block of S (R x N) is small.
+// and backward: the row statistics (dvc_cx_rows), the column maxima (dvc_cx_colmax), the loss (dvc_cx_finish), the T / Q row
+// sums (dvc_cx_rows_tq) and dS (dvc_cx_ds).  The centre-and-normalise step in front and its backward (dvc_cx_prepare,
+// dvc_cx_normalize_bwd) are in feature_norm.hip.  Feature maps on this path have N <= 1296 positions (27x48), so a block of S
+// (R x N) is small.
 #include "common.h"
 
 #include <cmath>
 
-// ---- centre (with a GIVEN or own per-channel mean) + L2-normalise over channels; also returns the norms (for backward)
-__global__ __launch_bounds__(256) void cx_rowmean_kernel(const float* __restrict__ t, int P, float* __restrict__ mean) {
-    __shared__ double red[4];
-    const float* row = t + (long)blockIdx.x * P;
-    double s = 0.0;
-    for (int i = threadIdx.x; i < P; i += 256) s += (double)row[i];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) mean[blockIdx.x] = (float)((red[0] + red[1] + red[2] + red[3]) / (double)P);
-}
+#include "reduce.h"
 
-// (r06: 16 channel groups x 64 positions per workgroup and four channel rows in flight per thread.  With 4 groups and one load
-// at a time a thread walked C / 4 = 128 dependent round trips twice and the grid was P / 64 x B workgroups — 72 us for 16 maps of
-// 512 x 13 x 24, 42 % of the contextual loss's GPU time at relu5_1)
-#define CX_NG 16
-__global__ __launch_bounds__(64 * CX_NG) void cx_normalize_kernel(const float* __restrict__ t, const float* __restrict__ mean, int C,
-                                                                  int P, float eps, float* __restrict__ out,
-                                                                  float* __restrict__ norm) {
-    __shared__ float part[CX_NG][64];
-    const int px = threadIdx.x & 63, g = threadIdx.x >> 6;
-    const int p = blockIdx.x * 64 + px;
-    const int b = blockIdx.y;
-    const float* tb = t + (long)b * C * P;
-    const float* mb = mean ? mean + (long)b * C : nullptr;
-    float* ob = out + (long)b * C * P;
-    const bool ok = p < P;
-    float s = 0.f;
-    if (ok) {
-        int c = g;
-        for (; c + 3 * CX_NG < C; c += 4 * CX_NG) {
-            float v[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) v[u] = tb[(long)(c + u * CX_NG) * P + p] - (mb ? mb[c + u * CX_NG] : 0.f);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) s = fmaf(v[u], v[u], s);
-        }
-        for (; c < C; c += CX_NG) {
-            const float v = tb[(long)c * P + p] - (mb ? mb[c] : 0.f);
-            s = fmaf(v, v, s);
-        }
-    }
-    part[g][px] = s;
-    __syncthreads();
-    float tot = 0.f;
-#pragma unroll
-    for (int k = 0; k < CX_NG; ++k) tot += part[k][px];        // fixed order
-    const float n = sqrtf(tot);
-    if (ok) {
-        if (g == 0 && norm) norm[(long)b * P + p] = n;
-        int c = g;
-        for (; c + 3 * CX_NG < C; c += 4 * CX_NG) {
-            float v[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) v[u] = tb[(long)(c + u * CX_NG) * P + p] - (mb ? mb[c + u * CX_NG] : 0.f);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) ob[(long)(c + u * CX_NG) * P + p] = v[u] / (n + eps);
-        }
-        for (; c < C; c += CX_NG) ob[(long)c * P + p] = (tb[(long)c * P + p] - (mb ? mb[c] : 0.f)) / (n + eps);
-    }
-}
-
-extern "C" int dvc_cx_prepare(const float* x, const float* mean_in, int32_t centre, int32_t B, int32_t C, int32_t P, float eps,
-                              float* mean_out, float* norm_out, float* out, dvcStream stream) {
-    DVC_REQUIRE(x && out && B > 0 && C > 0 && P > 0, "dvc_cx_prepare: bad argument");
-    DVC_REQUIRE(!centre || mean_in || mean_out, "dvc_cx_prepare: centring needs a mean to use or a place to put its own");
-    hipStream_t s = (hipStream_t)stream;
-    const float* mean = nullptr;
-    if (centre) {
-        mean = mean_in;
-        if (!mean) {
-            hipLaunchKernelGGL(cx_rowmean_kernel, dim3(B * C), dim3(256), 0, s, x, P, mean_out);
-            DVC_CHECK_LAUNCH("dvc_cx_prepare(mean)");
-            mean = mean_out;
-        }
-    }
-    hipLaunchKernelGGL(cx_normalize_kernel, dim3(cdiv(P, 64), B), dim3(64 * CX_NG), 0, s, x, mean, C, P, eps, out, norm_out);
-    DVC_CHECK_LAUNCH("dvc_cx_prepare(normalise)");
-    return 0;
-}
+#define CX_NG 16        // row groups of cx_colmax_kernel
 
 // ---- per row of a block of S (rows x N): a_i = (1 - max_j S_ij) + 1e-5, arg-max j*_i (lowest index on ties),
 // l_i = sum_j w_ij, r_i = max_j A_ij = w_{i j*} / l_i, E_i = sum_j A_ij d_ij.  One workgroup per row.
@@ -137,13 +62,12 @@ __global__ __launch_bounds__(256) void cx_rows_kernel(const float* __restrict__ 
         l += w;
         e = fmaf(w, 1.f - s[j], e);
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { l += __shfl_xor(l, off, 64); e += __shfl_xor(e, off, 64); }
-    if ((threadIdx.x & 63) == 0) { red2[0][threadIdx.x >> 6] = l; red2[1][threadIdx.x >> 6] = e; }
+    wave_store(wave_sum(l), red2[0]);
+    wave_store(wave_sum(e), red2[1]);
     __syncthreads();
     if (threadIdx.x == 0) {
-        l = (red2[0][0] + red2[0][1]) + (red2[0][2] + red2[0][3]);
-        e = (red2[1][0] + red2[1][1]) + (red2[1][2] + red2[1][3]);
+        l = tree_sum4(red2[0]);
+        e = tree_sum4(red2[1]);
         a_out[row] = a;
         jstar[row] = mi;
         l_out[row] = l;
@@ -233,12 +157,9 @@ __global__ __launch_bounds__(256) void cx_finish_kernel(const float* __restrict_
     double s = 0.0;
     v += (long)blockIdx.x * n; loss += blockIdx.x; gscale += blockIdx.x;      // image blockIdx.x of a [B][n] array
     for (int i = threadIdx.x; i < n; i += 256) s += (double)v[i];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
+    s = block_chain_sum<4>(wave_sum(s), red);
     if (threadIdx.x == 0) {
-        const double cx = (red[0] + red[1] + red[2] + red[3]) / (double)n;
+        const double cx = s / (double)n;
         *loss = (float)(-log(cx));
         *gscale = (float)(-1.0 / ((double)n * cx));
     }
@@ -270,13 +191,12 @@ __global__ __launch_bounds__(256) void cx_rows_tq_kernel(const float* __restrict
             t += A;
             q = fmaf(A, 1.f - s[j], q);
         }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { t += __shfl_xor(t, off, 64); q += __shfl_xor(q, off, 64); }
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = t; red[1][threadIdx.x >> 6] = q; }
+    wave_store(wave_sum(t), red[0]);
+    wave_store(wave_sum(q), red[1]);
     __syncthreads();
     if (threadIdx.x == 0) {
-        t_out[row] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-        q_out[row] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+        t_out[row] = tree_sum4(red[0]);
+        q_out[row] = tree_sum4(red[1]);
     }
 }
 
@@ -363,64 +283,5 @@ extern "C" int dvc_cx_rows_tq(const float* S, int32_t nb, int64_t S_bs, int64_t 
     hipLaunchKernelGGL(cx_rows_tq_kernel, dim3(rows, nb), dim3(256), 0, (hipStream_t)stream, S, (long)S_bs, (long)row_bs, (long)tq_bs, a,
                        l, cargi, N, row0, h, t, q);
     DVC_CHECK_LAUNCH("dvc_cx_rows_tq");
-    return 0;
-}
-
-// ---- backward of  xn = xc / (||xc|| + eps):  d xc_k = d xn_k / (n + eps) - xn_k (xn . d xn) / n
-__global__ __launch_bounds__(64 * CX_NG) void cx_normalize_bwd_kernel(const float* __restrict__ xn, const float* __restrict__ norm,
-                                                                      const float* __restrict__ dxn, int C, int P, float eps,
-                                                                      float* __restrict__ dx) {
-    __shared__ float part[CX_NG][64];
-    const int px = threadIdx.x & 63, g = threadIdx.x >> 6;
-    const int p = blockIdx.x * 64 + px;
-    const int b = blockIdx.y;
-    const long base = (long)b * C * P + p;
-    const bool ok = p < P;
-    float s = 0.f;
-    if (ok) {
-        int c = g;
-        for (; c + 3 * CX_NG < C; c += 4 * CX_NG) {
-            float a[4], d[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                a[u] = xn[base + (long)(c + u * CX_NG) * P];
-                d[u] = dxn[base + (long)(c + u * CX_NG) * P];
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) s = fmaf(a[u], d[u], s);
-        }
-        for (; c < C; c += CX_NG) s = fmaf(xn[base + (long)c * P], dxn[base + (long)c * P], s);
-    }
-    part[g][px] = s;
-    __syncthreads();
-    float dot = 0.f;
-#pragma unroll
-    for (int k = 0; k < CX_NG; ++k) dot += part[k][px];        // fixed order
-    if (ok) {
-        const float n = norm[(long)b * P + p];
-        const float inv = 1.f / (n + eps), k = n > 0.f ? dot / n : 0.f;
-        int c = g;
-        for (; c + 3 * CX_NG < C; c += 4 * CX_NG) {
-            float a[4], d[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                a[u] = xn[base + (long)(c + u * CX_NG) * P];
-                d[u] = dxn[base + (long)(c + u * CX_NG) * P];
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) dx[base + (long)(c + u * CX_NG) * P] = d[u] * inv - a[u] * k;
-        }
-        for (; c < C; c += CX_NG) {
-            const long o = base + (long)c * P;
-            dx[o] = dxn[o] * inv - xn[o] * k;
-        }
-    }
-}
-
-extern "C" int dvc_cx_normalize_bwd(const float* xn, const float* norm, const float* dxn, int32_t B, int32_t C, int32_t P, float eps,
-                                    float* dx, dvcStream stream) {
-    DVC_REQUIRE(xn && norm && dxn && dx && B > 0 && C > 0 && P > 0, "dvc_cx_normalize_bwd: bad argument");
-    hipLaunchKernelGGL(cx_normalize_bwd_kernel, dim3(cdiv(P, 64), B), dim3(64 * CX_NG), 0, (hipStream_t)stream, xn, norm, dxn, C, P, eps, dx);
-    DVC_CHECK_LAUNCH("dvc_cx_normalize_bwd");
     return 0;
 }

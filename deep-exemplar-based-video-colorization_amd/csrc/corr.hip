@@ -34,98 +34,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 #define CORR_NF 7         // fields per partial state: m, l, y0, y1, y2, fmax, argmax
 
 // ------------------------------------------------------------------------------------------------
-// corr_prepare: per-channel mean over positions, then per-position L2 normalisation over channels
-__global__ __launch_bounds__(256) void corr_rowmean_kernel(const float* __restrict__ t, int P,
-                                                           float* __restrict__ mean) {
-    __shared__ double red[4];
-    const float* row = t + (long)blockIdx.x * P;
-    double s = 0.0;
-    for (int i = threadIdx.x; i < P; i += 256) s += (double)row[i];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) mean[blockIdx.x] = (float)((red[0] + red[1] + red[2] + red[3]) / (double)P);
-}
-
-// float4 form (P % 4 == 0, aligned): workgroup = 32 positions (8 lanes x float4: one 128-byte line per channel row) x 32
-// channel groups — 162 workgroups at P = 5184 with 8 channels per thread and pass, where the scalar form below runs 81
-// workgroups of 64-deep serial loops (27 us for 10.6 MB: pure latency).
-__global__ __launch_bounds__(256) void corr_normalize_v4_kernel(const float* __restrict__ t, const float* __restrict__ mean,
-                                                                int C, int P, float eps, float* __restrict__ out) {
-    __shared__ float4 part[32][8];
-    const int px4 = threadIdx.x & 7, g = threadIdx.x >> 3;
-    const int p = (blockIdx.x * 8 + px4) * 4;
-    const int b = blockIdx.y;
-    const float* tb = t + (long)b * C * P;
-    const float* mb = mean + (long)b * C;
-    float* ob = out + (long)b * C * P;
-    const bool ok = p < P;
-    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (ok)
-        for (int c = g; c < C; c += 32) {
-            const float4 v = *reinterpret_cast<const float4*>(tb + (long)c * P + p);
-            const float mu = mb[c];
-            const float a0 = v.x - mu, a1 = v.y - mu, a2 = v.z - mu, a3 = v.w - mu;
-            s.x = fmaf(a0, a0, s.x); s.y = fmaf(a1, a1, s.y); s.z = fmaf(a2, a2, s.z); s.w = fmaf(a3, a3, s.w);
-        }
-    part[g][px4] = s;
-    __syncthreads();
-    float4 tt = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-    for (int k = 0; k < 32; ++k) {
-        const float4 v = part[k][px4];
-        tt.x += v.x; tt.y += v.y; tt.z += v.z; tt.w += v.w;
-    }
-    const float d0 = sqrtf(tt.x) + eps, d1 = sqrtf(tt.y) + eps, d2 = sqrtf(tt.z) + eps, d3 = sqrtf(tt.w) + eps;
-    if (ok)
-        for (int c = g; c < C; c += 32) {
-            const float4 v = *reinterpret_cast<const float4*>(tb + (long)c * P + p);
-            const float mu = mb[c];
-            *reinterpret_cast<float4*>(ob + (long)c * P + p) = make_float4((v.x - mu) / d0, (v.y - mu) / d1, (v.z - mu) / d2, (v.w - mu) / d3);
-        }
-}
-
-__global__ __launch_bounds__(256) void corr_normalize_kernel(const float* __restrict__ t,
-                                                             const float* __restrict__ mean, int C, int P,
-                                                             float eps, float* __restrict__ out) {
-    __shared__ float part[4][64];
-    const int px = threadIdx.x & 63, g = threadIdx.x >> 6;
-    const int p = blockIdx.x * 64 + px;
-    const int b = blockIdx.y;
-    const float* tb = t + (long)b * C * P;
-    const float* mb = mean + (long)b * C;
-    float* ob = out + (long)b * C * P;
-    const bool ok = p < P;
-    float s = 0.f;
-    if (ok)
-        for (int c = g; c < C; c += 4) {
-            float v = tb[(long)c * P + p] - mb[c];
-            s = fmaf(v, v, s);
-        }
-    part[g][px] = s;
-    __syncthreads();
-    float den = sqrtf(part[0][px] + part[1][px] + part[2][px] + part[3][px]) + eps;
-    if (ok)
-        for (int c = g; c < C; c += 4) ob[(long)c * P + p] = (tb[(long)c * P + p] - mb[c]) / den;
-}
-
-extern "C" int dvc_corr_prepare(const float* t_raw, int32_t B, int32_t C, int32_t P, float eps,
-                                float* mean_scratch, float* t_out, dvcStream stream) {
-    DVC_REQUIRE(t_raw && mean_scratch && t_out && B > 0 && C > 0 && P > 0, "dvc_corr_prepare: bad argument");
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(corr_rowmean_kernel, dim3(B * C), dim3(256), 0, s, t_raw, P, mean_scratch);
-    DVC_CHECK_LAUNCH("dvc_corr_prepare(mean)");
-    if (P % 4 == 0 && (((reinterpret_cast<uintptr_t>(t_raw) | reinterpret_cast<uintptr_t>(t_out)) & 15) == 0))
-        hipLaunchKernelGGL(corr_normalize_v4_kernel, dim3(cdiv(P, 32), B), dim3(256), 0, s, t_raw, mean_scratch, C, P, eps, t_out);
-    else
-        hipLaunchKernelGGL(corr_normalize_kernel, dim3(cdiv(P, 64), B), dim3(256), 0, s, t_raw, mean_scratch, C,
-                           P, eps, t_out);
-    DVC_CHECK_LAUNCH("dvc_corr_prepare(normalise)");
-    return 0;
-}
-
-// ------------------------------------------------------------------------------------------------
 struct CorrArgs {
     const float* theta;
     const float* phi;

@@ -24,9 +24,11 @@
 //                                 against ALL keys (exact, just slower).
 // Layouts: bf16 and fp32 copies of theta/phi as [P][C] (channel-contiguous): an MFMA fragment is one
 // 16-byte load, a candidate's fp32 column is one contiguous 1 KB row.
-#include "common.h"
+#include "feature_norm.h"
 
 #include <cmath>
+
+#include "reduce.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -49,7 +51,7 @@ __device__ __forceinline__ unsigned short f32_to_bf16_rne(float f) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// centre + normalise (as corr_prepare) but emit [P][C] fp32 and [P][C] bf16
+// centre + normalise (as dvc_corr_prepare, on feature_norm.hip's row mean) but emit [P][C] fp32 and [P][C] bf16
 __global__ __launch_bounds__(256) void corr_prepare_t_kernel(const float* __restrict__ t,
                                                              const float* __restrict__ mean, int P, float eps,
                                                              float* __restrict__ out_f32,
@@ -93,25 +95,12 @@ __global__ __launch_bounds__(256) void corr_prepare_t_kernel(const float* __rest
     }
 }
 
-__global__ __launch_bounds__(256) void corr_rowmean2_kernel(const float* __restrict__ t, int P,
-                                                            float* __restrict__ mean) {
-    __shared__ double red[4];
-    const float* row = t + (long)blockIdx.x * P;
-    double s = 0.0;
-    for (int i = threadIdx.x; i < P; i += 256) s += (double)row[i];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) mean[blockIdx.x] = (float)((red[0] + red[1] + red[2] + red[3]) / (double)P);
-}
-
 extern "C" int dvc_corr_prepare_bf16(const float* t_raw, int32_t B, int32_t C, int32_t P, float eps,
                                      float* mean_scratch, float* t_f32_pc, void* t_bf16_pc, dvcStream stream) {
     DVC_REQUIRE(t_raw && mean_scratch && t_f32_pc && t_bf16_pc && B > 0 && P > 0, "dvc_corr_prepare_bf16: bad argument");
     DVC_REQUIRE(C == CB_C, "dvc_corr_prepare_bf16: C must be %d", CB_C);
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(corr_rowmean2_kernel, dim3(B * C), dim3(256), 0, s, t_raw, P, mean_scratch);
+    feature_rowmean_launch(t_raw, B * C, P, mean_scratch, s);
     DVC_CHECK_LAUNCH("dvc_corr_prepare_bf16(mean)");
     hipLaunchKernelGGL(corr_prepare_t_kernel, dim3(cdiv(P, 32), B), dim3(256), 0, s, t_raw, mean_scratch, P, eps,
                        t_f32_pc, reinterpret_cast<unsigned short*>(t_bf16_pc));
@@ -416,8 +405,7 @@ __global__ __launch_bounds__(256) void corr_bf16_rescore_kernel(const float* __r
             const int k = __shfl(key, i, 64);
             const float4 kv = *reinterpret_cast<const float4*>(pb + (long)k * CB_C + lane * 4);
             float f = fmaf(qv.w, kv.w, fmaf(qv.z, kv.z, fmaf(qv.y, kv.y, qv.x * kv.x)));
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) f += __shfl_xor(f, off, 64);
+            f = wave_sum(f);
             fmine = lane == i ? f : fmine;
         }
         if (lane < n) accumulate(key, fmine);

@@ -12,6 +12,8 @@
 
 #include <cmath>
 
+#include "reduce.h"
+
 // m_i = max_j fl32(F_ij / T),  l_i = sum_j exp(fl32(F_ij / T) - m_i): ATen's softmax arithmetic (true division, exp of the
 // difference to the row maximum), one workgroup per row.  The maximum is taken over the block as RECOMPUTED here (the
 // forward kernel's similarity comes from another summation order and need not bound it: at T <= 1e-7 an excess of one
@@ -36,30 +38,19 @@ __global__ __launch_bounds__(256) void corr_bwd_rowstat_kernel(const float* __re
     float raw = -INFINITY;
     if (wta != 1.f) {       // (block-uniform) raw row maximum first: it decides which elements are re-weighted
         for (int j = threadIdx.x; j < P; j += 256) raw = fmaxf(raw, f[j]);
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) raw = fmaxf(raw, __shfl_xor(raw, off, 64));
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = raw;
-        __syncthreads();
-        raw = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-        __syncthreads();
+        raw = block_tree_max4(wave_max(raw), red);
+        __syncthreads();        // (red is reused below)
     }
     float mx = -INFINITY;
     for (int j = threadIdx.x; j < P; j += 256) mx = fmaxf(mx, wta_apply(f[j], raw, wta) / T);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
-    __syncthreads();
-    const float m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    const float m = block_tree_max4(wave_max(mx), red);
     __syncthreads();
     float s = 0.f;
     for (int j = threadIdx.x; j < P; j += 256) s += expf(wta_apply(f[j], raw, wta) / T - m);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
+    s = block_tree_sum4(wave_sum(s), red);
     if (threadIdx.x == 0) {
         m_out[row] = m;
-        l_out[row] = (red[0] + red[1]) + (red[2] + red[3]);
+        l_out[row] = s;
         raw_out[row] = raw;
     }
 }

@@ -144,11 +144,8 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
                 s1 = fmaf(d1, r, s1);
             }
         }
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) {
-            s0 += __shfl_xor(s0, m);
-            s1 += __shfl_xor(s1, m);
-        }
+        s0 = wave_sum(s0);
+        s1 = wave_sum(s1);
         if (lane == 0) {
             slot[c] = s0;
             slot[C + c] = s1;

@@ -31,6 +31,8 @@
 #include <cmath>
 #include <cstdint>
 
+#include "reduce.h"
+
 #define FW_TW 64
 #define FW_TH 4
 #define FW_MAX_HW (1L << 22)
@@ -100,11 +102,8 @@ __global__ __launch_bounds__(256) void fw_amax_kernel(const float* __restrict__ 
     const unsigned* g = reinterpret_cast<const unsigned*>(G) + (long)b * n;
     unsigned m = 0;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) m = max(m, g[i] & 0x7fffffffu);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) atomicMax(amax_bits + 2 * b, max(max(red[0], red[1]), max(red[2], red[3])));
+    m = block_tree_max4(wave_max(m), red);
+    if (threadIdx.x == 0) atomicMax(amax_bits + 2 * b, m);
 }
 
 // 2^k as a double, k within the normal range

@@ -1,11 +1,11 @@
 // WarpNet's backward behind the trunk tensor (training mode, dvc_amd/nets.py): the residual blocks, the theta / phi projections,
 // the centre-and-normalise step and the x4 nearest upsample.  The 3x3 input gradients run on the forward's engines (zero pad 1 on
 // a zero-ringed map, W^T flipped), the 3x3 weight gradients on dvc_cvn_wgrad (zero-ringed dZ against a reflect-padded copy of
-// the input), the correlation on dvc_amd/corr_autograd.py; what is here is the steps between them:
+// the input), the correlation on dvc_amd/corr_autograd.py, the centre-and-normalise step's backward on dvc_warp_cn_bwd
+// (feature_norm.hip); what is here is the steps between them:
 //   dvc_warp_up4_bwd         4x4 block sums (backward of the x4 nearest upsample)
 //   dvc_warp_prelu_fwd       y = prelu(n [+ skip]) — the forward's activation as a launch of its own, so that the norm's output
 //                            exists as a tensor
-//   dvc_warp_cn_bwd          backward of t -> (t - mean_P t) / (||t - mean_P t||_2 + eps)
 //   dvc_warp_k1_wgrad        dW = sum_n dT[n] F[n]^T, db = sum dT of a 1x1 convolution on v_mfma_f32_32x32x2_f32
 //   dvc_warp_norm_prelu_bwd  PReLU + InstanceNorm backward per plane into a zero-ringed map (+ the skip's gradient, the slope's
 //                            partial sum)
@@ -49,52 +49,6 @@ __global__ __launch_bounds__(256) void prelu_fwd_kernel(const float* __restrict_
         if (res) v += res[i];
         y[i] = v >= 0.f ? v : v * slope;       // (the expression of instnorm_apply_plane, csrc/norm_pool.hip)
     }
-}
-
-// ------------------------------------------------------------------------------------------------ centre-and-normalise backward
-// Step 1, per position (64 positions x 4 channel groups per workgroup): tc = t - mean, r = ||tc||, s = r + eps,
-// d tc = g / s - tc (tc . g) / (r s^2)   (the second term is zero where r == 0).  The two channel sums run in double.
-__global__ __launch_bounds__(256) void cn_bwd_pos_kernel(const float* __restrict__ t, const float* __restrict__ mean,
-                                                         const float* __restrict__ g, int C, int P, float eps,
-                                                         float* __restrict__ dtc) {
-    __shared__ double pss[4][64], pdot[4][64];
-    const int px = threadIdx.x & 63, grp = threadIdx.x >> 6;
-    const int p = blockIdx.x * 64 + px, b = blockIdx.y;
-    const float* tb = t + (long)b * C * P;
-    const float* gb = g + (long)b * C * P;
-    const float* mb = mean + (long)b * C;
-    float* ob = dtc + (long)b * C * P;
-    const bool ok = p < P;
-    double ss = 0.0, dot = 0.0;
-    if (ok)
-        for (int c = grp; c < C; c += 4) {
-            const float v = tb[(long)c * P + p] - mb[c];
-            ss += (double)v * (double)v;
-            dot += (double)v * (double)gb[(long)c * P + p];
-        }
-    pss[grp][px] = ss;
-    pdot[grp][px] = dot;
-    __syncthreads();
-    const double SS = (pss[0][px] + pss[1][px]) + (pss[2][px] + pss[3][px]);
-    const double DOT = (pdot[0][px] + pdot[1][px]) + (pdot[2][px] + pdot[3][px]);
-    const double r = sqrt(SS), s = r + (double)eps;
-    const float inv_s = (float)(1.0 / s);
-    const float k = r > 0.0 ? (float)(DOT / (r * s * s)) : 0.f;
-    if (ok)
-        for (int c = grp; c < C; c += 4) {
-            const float v = tb[(long)c * P + p] - mb[c];
-            ob[(long)c * P + p] = gb[(long)c * P + p] * inv_s - v * k;
-        }
-}
-
-// Step 2, per (image, channel) row: d t = d tc - mean_P(d tc), in place; the mean in double, rounded once.
-__global__ __launch_bounds__(256) void cn_bwd_center_kernel(float* __restrict__ d, int P) {
-    __shared__ double red[4];
-    float* row = d + (long)blockIdx.x * P;
-    double s = 0.0;
-    for (int i = threadIdx.x; i < P; i += 256) s += (double)row[i];
-    const float m = (float)(block_sum<double, 256>(s, red) / (double)P);
-    for (int i = threadIdx.x; i < P; i += 256) row[i] -= m;
 }
 
 // ------------------------------------------------------------------------------------------------ 1x1 weight gradient
@@ -298,20 +252,6 @@ extern "C" int dvc_warp_prelu_fwd(const float* n, const float* skip, const float
     DVC_REQUIRE(count > 0, "dvc_warp_prelu_fwd: bad size (%ld)", (long)count);
     hipLaunchKernelGGL(prelu_fwd_kernel, dim3(grid_for(count)), dim3(256), 0, (hipStream_t)stream, n, skip, slope, (long)count, y);
     DVC_CHECK_LAUNCH("dvc_warp_prelu_fwd");
-    return 0;
-}
-
-extern "C" int dvc_warp_cn_bwd(const float* t_raw, const float* mean, const float* g, int32_t B, int32_t C, int32_t P, float eps,
-                               float* dt, dvcStream stream) {
-    DVC_REQUIRE(t_raw && mean && g && dt, "dvc_warp_cn_bwd: null pointer");
-    DVC_REQUIRE(B > 0 && C > 0 && P > 0, "dvc_warp_cn_bwd: bad size (B %d C %d P %d)", B, C, P);
-    DVC_REQUIRE(B <= 65535 && (long)B * C < (1L << 31), "dvc_warp_cn_bwd: batch too large");
-    DVC_REQUIRE(dt != t_raw && dt != g && dt != mean, "dvc_warp_cn_bwd: dt must not alias an input");
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(cn_bwd_pos_kernel, dim3(cdiv(P, 64), B), dim3(256), 0, st, t_raw, mean, g, (int)C, (int)P, eps, dt);
-    DVC_CHECK_LAUNCH("dvc_warp_cn_bwd (positions)");
-    hipLaunchKernelGGL(cn_bwd_center_kernel, dim3(B * C), dim3(256), 0, st, dt, (int)P);
-    DVC_CHECK_LAUNCH("dvc_warp_cn_bwd (centre)");
     return 0;
 }
 

@@ -148,6 +148,49 @@ def test_channel_l2norm_multi_takes_eight_maps_and_rejects_nine(ops):
     assert rc != 0 and b"dvc_channel_l2norm_multi" in lib.dvc_last_error()
 
 
+# ---- dvc_cx_prepare: the same normalise with 16 channel groups, an optional mean and the norms
+# C = 8, 3: fewer channels than groups (empty groups); 66: uneven groups and the tail of the four-in-flight loop; 130: one full
+# round of it.  P = 1, 63, 100: below one 64-position tile, ragged across two.  Unit-scale inputs, |out| <= 1: the tolerance of
+# the channel_l2norm cases above (the centring adds one rounding of the mean and one of the subtraction per value).
+@pytest.mark.parametrize("centre", ["own", "given", "none"])
+@pytest.mark.parametrize("C,P", [(8, 100), (3, 1), (66, 63), (130, 100)])
+def test_cx_prepare_edges(ops, C, P, centre):
+    from cabi_helpers import check, nan_tensor, ptr
+    from dvc_amd import _lib
+    from oracle import contextual_oracle as CO
+    lib = _lib.load()
+    B = 2
+    x = torch.randn(B, C, P, generator=_gen(C, P))
+    x[0, :, 0] = 0.0                    # a position whose channels are all zero
+    given = torch.randn(B * C, generator=_gen(P, C)) * 0.1
+    xd = x.cuda()
+    out, mean, norm = nan_tensor(B, C, P), nan_tensor(B * C), nan_tensor(B, P)
+    if centre == "own":
+        rc = lib.dvc_cx_prepare(ptr(xd), None, 1, B, C, P, ops.EPS64, ptr(mean), None, ptr(out), ops._stream())
+        mu = x.double().mean(-1)
+        assert (mean.cpu().double() - mu.flatten()).abs().max().item() < 2e-7
+    elif centre == "given":
+        rc = lib.dvc_cx_prepare(ptr(xd), ptr(given.cuda()), 1, B, C, P, ops.EPS64, None, ptr(norm), ptr(out), ops._stream())
+        mu = given.double().view(B, C)
+    else:
+        rc = lib.dvc_cx_prepare(ptr(xd), None, 0, B, C, P, ops.EPS64, None, ptr(norm), ptr(out), ops._stream())
+        mu = torch.zeros(B, C, dtype=torch.float64)
+    check(rc, "dvc_cx_prepare")
+    xc = x.double() - mu.unsqueeze(-1)
+    assert not torch.isnan(out).any()
+    assert (out.cpu().double() - CO.feature_normalize(xc)).abs().max().item() < 2e-7
+    if centre == "none":
+        assert (out[0, :, 0] == 0).all()
+    if centre != "own":
+        # the norm: every square carries the subtraction's rounding twice, the sum at most ceil(C / 16) + 16 roundings (fmaf
+        # chain per group, then the groups), the root halves the relative error and adds one rounding of its own
+        n64 = xc.norm(dim=1)
+        rel = ((C + 15) // 16 + 16 + 2) / 2 * 2.0 ** -24 + 2.0 ** -24
+        err = (norm.cpu().double() - n64).abs()
+        print(f"norm: max relative error {(err / n64.clamp_min(1e-30)).max().item():.3e}, bound {rel:.3e}")
+        assert (err <= rel * n64).all()
+
+
 # ---- dvc_affine_act / dvc_instnorm_apply index maps
 def _rows_replicated(r, rpad):
     if rpad == 0:
