@@ -629,6 +629,11 @@ static int wino_setup(const DvcConvDesc* d, const DvcConvDesc* d2, const float* 
         a.x_bs = d->x_batch_stride ? d->x_batch_stride : (long)s.cinA * d->H * d->W;
     }
     wino_plan(d, OH, OW, workspace != nullptr, workspace_bytes, &best_m, &best_tr, &best_S, d2 ? 2 : -1);
+    // (the planner passes over a split whose partial sums of ONE image exceed the workspace, so a forced split_k ends here and
+    // never at the `group > 0` check below: name the cause)
+    DVC_REQUIRE(best_m >= 0 || !(d->split_k > 1 && workspace && (size_t)d->split_k * d->Cout * OH * OW * sizeof(float) > workspace_bytes),
+                "dvc_conv2d_winograd: split-K workspace too small for one image (split_k %d needs %zu bytes, got %zu)", d->split_k,
+                (size_t)d->split_k * d->Cout * OH * OW * sizeof(float), workspace_bytes);
     DVC_REQUIRE(best_m >= 0, "dvc_conv2d_winograd: no configuration for cfg %d / split_k %d on this layer", d->cfg, d->split_k);
     const int wm = kWinoShapes[best_m].wm, wn = kWinoShapes[best_m].wn, kc = kWinoShapes[best_m].kc;
     const int nch = d->Cin / kc;

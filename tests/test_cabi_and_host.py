@@ -245,6 +245,80 @@ def test_batch_plan_flag_trades_the_split_for_the_batch():
     assert not ops.batch_plan_enabled()
 
 
+def _wino_split(lib, ws, *shape, **kw):
+    import ctypes
+    from dvc_amd import ops
+    d = ops._conv_desc(*shape, **kw)
+    sp, ipl = ctypes.c_int32(0), ctypes.c_int32(0)
+    assert lib.dvc_conv2d_winograd_split(ctypes.byref(d), ws, ctypes.byref(sp), ctypes.byref(ipl)) == 0, lib.dvc_last_error()
+    return sp.value, ipl.value
+
+
+def test_winograd_plans_of_the_multi_pass_cases():
+    """Host logic, no GPU: the (split, images_per_launch) of every case of tests/test_gpu_conv_batch_passes.py, so that a change
+    of the planner that would quietly turn those cases into single-pass launches fails here first; and the two refusals of
+    dvc_conv2d_winograd that are decided before any launch."""
+    import ctypes
+    from dvc_amd import _lib, ops
+    lib = _lib.load()
+    H, W, N = 13, 23, 5
+    per = 64 * H * W * 4                      # bytes of one image's output, Cout = 64
+    # workspace-limited: the workspace holds the partial sums of k of the 5 images
+    for dil, S, k in [(1, 2, 2), (1, 3, 2), (2, 2, 2), (1, 2, 1)]:
+        assert _wino_split(lib, k * S * per, N, 64, H, W, 64, dil=dil, act=1, split_k=S) == (S, k)
+    assert _wino_split(lib, 2 * 2 * per, N, 16, H, W, 64, act=1, split_k=2) == (2, 2)                                  # pool
+    assert _wino_split(lib, 2 * 2 * 64 * 14 * 22 * 4, N, 16 + 24, 14, 22, 64, act=1, cfg=9, split_k=2) == (2, 2)       # dual
+    # the 65535-workgroup cap: cfg, split, Cin, H x W, dil, workgroups per image, N
+    for cfg, S, Cin, h, dil, per_image, n in [(12, 1, 8, 2, 1, 2, 32770), (8, 2, 16, 2, 1, 2, 32770), (8, 1, 8, 4, 2, 4, 16386)]:
+        ws = 64 << 20 if S > 1 else 4096
+        sp, ipl = _wino_split(lib, ws, n, Cin, h, h, 64, dil=dil, act=1, cfg=cfg, split_k=S)
+        assert (sp, ipl) == (S, 65535 // per_image) and n - ipl == 3
+        assert ipl * per_image < 65536 <= (ipl + 1) * per_image       # index 65536 is never handed to the 16-bit decode
+        if S > 1:
+            assert ws // (S * 64 * h * h * 4) == 32768 > ipl          # the workspace alone would allow one image more
+    # dvc_amd.ops cases: 8192 images at 8 workgroups each are one workgroup too many; conv3x3_group's two layers
+    assert _wino_split(lib, 64 << 20, 8192, 64, 2, 2, 64, act=1, split_k=8) == (8, 8191)
+    assert 8 * 8192 * 64 * 2 * 2 * 4 == ops.CONV_WORKSPACE_BYTES
+    for Cin in (64, 128):
+        S = _wino_split(lib, ops.CONV_WORKSPACE_BYTES, N, Cin, 13, 25, 64, act=1)[0]
+        assert S > 1 and _wino_split(lib, 2 * S * 64 * 13 * 25 * 4, N, Cin, 13, 25, 64, act=1) == (S, 2)
+    # a single image that needs 65536 workgroups or more is not planned into a launch (-1; the launcher refuses it)
+    assert _wino_split(lib, 4096, 1, 8, 2048, 2048, 64, cfg=12, split_k=1) == (1, -1)
+    # refused before any launch (no pointer is read): a workspace one byte short of ONE image at the forced split ...
+    one = ctypes.c_void_p(16)
+    d = ops._conv_desc(N, 64, H, W, 64, act=1, split_k=2)
+    rc = lib.dvc_conv2d_winograd(ctypes.byref(d), one, one, None, None, None, one, one, 2 * per - 1, None)
+    assert rc != 0 and b"too small for one image" in lib.dvc_last_error(), lib.dvc_last_error()
+    # ... and a deferred reduce with room for 2 of the 5 images
+    d = ops._conv_desc(N, 64, H, W, 64, act=1, split_k=2, flags=ops.DEFER_REDUCE)
+    rc = lib.dvc_conv2d_winograd(ctypes.byref(d), one, one, None, None, None, one, one, 2 * 2 * per, None)
+    assert rc != 0 and b"DVC_CONV_DEFER_REDUCE needs a workspace that holds the partial sums of the whole batch" in lib.dvc_last_error()
+
+
+def test_winograd_reciprocal_decode_is_exact_below_65536():
+    """csrc/conv_wino_kernel.h decodes the 1-D workgroup index with wino_div(n, wino_magic(d)) = umulhi(n, ceil(2^32 / d))
+    (d == 1: magic 0, quotient n) for d = gx * gy, gx, blk_y * blk_x, blk_x and split, all of them <= the grid size.  Restated
+    with integers: exact for every divisor 1 .. 65535 at the quotient boundaries of the index range the 65535-workgroup cap
+    allows (wino_images_per_launch).  The argument that makes it exact, n * (d * magic - 2^32) < 2^32, needs n < 65536 for
+    d up to 65535: the launcher must never build a grid of 65536 workgroups or more, which the plan test above pins."""
+    def magic(d):
+        return (2 ** 32 + d - 1) // d if d > 1 else 0
+
+    def div(n, m):
+        return (n * m) >> 32 if m else n
+
+    for d in range(1, 65536):
+        m = magic(d)
+        assert m < 2 ** 32
+        top = 65535 - 65535 % d
+        for n in (0, d - 1, d, top - 1, top, 65535):
+            assert div(n, m) == n // d, (n, d)
+        assert d == 1 or (d * m - 2 ** 32) * 65535 < 2 ** 32          # the sufficient condition holds up to n = 65535
+    # ... and the reciprocal is NOT exact for every larger index (e.g. 93015 / 46508 decodes as 2): the cap is what keeps the
+    # decode right, and 65536 is not claimed
+    assert div(93015, magic(46508)) == 2 != 93015 // 46508
+
+
 def test_bench_torchrun_relaunch_command():
     """`python bench.py --gpus N` re-launches itself as the driver does (one rank per GPU under torch.distributed.run, 127.0.0.1
     rendezvous, its own flags passed through): the command line is built here without launching anything."""
