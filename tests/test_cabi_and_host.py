@@ -295,6 +295,148 @@ def test_winograd_plans_of_the_multi_pass_cases():
     assert rc != 0 and b"DVC_CONV_DEFER_REDUCE needs a workspace that holds the partial sums of the whole batch" in lib.dvc_last_error()
 
 
+# ---- every refusal of the convolution entry points of csrc/conv_mfma.hip that is decided before any launch: (entry point,
+# descriptor shape (N, Cin, H, W, Cout), descriptor fields, argument overrides, substring of the message).  The messages were
+# recorded from the library before its launcher was split into check / plan / launch steps.  Arguments default to a dummy
+# non-NULL pointer (16) that nothing reads, since every row is refused; `ws`: workspace bytes (0: no workspace).
+_S = (1, 16, 8, 8, 32)
+_W = (1, 16, 8, 8, 64)
+_BIG = (1, 512, 1024, 1024, 64)
+CONV_REFUSALS = [
+    ("conv2d", None, {}, {}, "dvc_conv2d: null descriptor"),
+    ("conv2d", _S, {}, dict(x=None), "dvc_conv2d: null argument"),
+    ("conv2d", _S, {}, dict(y=None), "dvc_conv2d: null argument"),
+    ("conv2d", _S, dict(ksize=5, pad=2), {}, "dvc_conv2d: ksize must be 1 or 3 (got 5)"),
+    ("conv2d", _S, dict(stride=3), {}, "dvc_conv2d: stride must be 1 or 2"),
+    ("conv2d", _S, dict(dil=3, pad=2), {}, "dvc_conv2d: dilation must be 1 or 2"),
+    ("conv2d", _S, dict(pad=3), {}, "dvc_conv2d: pad must be 0..2"),
+    ("conv2d", (1, 16, 8, 8, 6), {}, {}, "dvc_conv2d: Cout must be a multiple of 4 (got 6)"),
+    ("conv2d", _S, dict(in_up=3), {}, "dvc_conv2d: bad in_up/in_sub"),
+    ("conv2d", _S, dict(in_up=2, in_sub=2), {}, "dvc_conv2d: bad in_up/in_sub"),
+    ("conv2d", _S, {}, dict(in_scale=16), "dvc_conv2d: scale/shift must come together"),
+    ("conv2d", _S, dict(in_prelu=True), {}, "dvc_conv2d: in_prelu needs in_slope_ptr"),
+    ("conv2d", (1, 0, 8, 8, 32), {}, {}, "dvc_conv2d: bad shape"),
+    ("conv2d", _S, {}, dict(w=20), "dvc_conv2d: weights must be 16-byte aligned"),
+    ("conv2d", (1, 1024, 2048, 1024, 32), {}, {}, "dvc_conv2d: tensor too large for 32-bit indexing"),
+    ("conv2d", (1, 16, 1, 1, 32), dict(pad=0), {}, "dvc_conv2d: empty output"),
+    ("conv2d", (1, 16, 1, 8, 32), dict(pad_mode=1), {}, "dvc_conv2d: reflect pad needs pad < input size"),
+    ("conv2d", _S, dict(w_batch_stride=6), {}, "dvc_conv2d: w_batch_stride must be a multiple of 4 (got 6)"),
+    ("conv2d", _W, dict(w_batch_stride=8, cfg=34), dict(ws=1 << 20), "dvc_conv2d: per-image filters run on the general engine only"),
+    ("conv2d", (1, 3, 8, 8, 64), dict(cfg=0, flags=4), {}, "dvc_conv2d: DVC_CONV_GRAY_INPUT is for the 3 -> 64 image-input layer"),
+    ("conv2d", _S, dict(ksize=1, stride=2, pad=0), {}, "dvc_conv2d: stride-2 / dilated variant supports ksize 3 only"),
+    ("conv2d", _W, dict(cfg=33), dict(ws=1 << 20), "dvc_conv2d: the stream-K path has tile configurations 2, 3 and 4 (cfg 34..36)"),
+    ("conv2d", _W, dict(cfg=37), dict(ws=1 << 20), "dvc_conv2d: the stream-K path has tile configurations 2, 3 and 4 (cfg 34..36)"),
+    ("conv2d", _W, dict(cfg=36), dict(ws=1 << 20, in_scale=16, in_shift=16),
+     "dvc_conv2d: the stream-K path needs a plain stride-1 layer (no fused input transform, Cin % 8 == 0, Cout % 64 == 0)"),
+    ("conv2d", _S, dict(cfg=34), dict(ws=1 << 20), "dvc_conv2d: the stream-K path needs a plain stride-1 layer"),
+    ("conv2d", _W, dict(cfg=36), {}, "dvc_conv2d: the stream-K path needs a workspace"),
+    ("conv2d", _BIG, dict(cfg=36), dict(ws=1 << 20), "dvc_conv2d: tensor too large for buffer-descriptor staging"),
+    ("conv2d", (1, 8, 4096, 4096, 262144), dict(cfg=36), dict(ws=1 << 20), "dvc_conv2d: too many tiles"),
+    ("conv2d", _W, dict(cfg=36), dict(ws=4096), "dvc_conv2d: workspace too small for the stream-K slots"),
+    ("conv2d", _S, dict(cfg=5), {}, "dvc_conv2d: cfg out of range"),
+    ("conv2d", _S, dict(cfg=21), {}, "dvc_conv2d: cfg out of range"),
+    ("conv2d", (1, 16, 64, 64, 32), dict(stride=2, dil=2, pad=2), {}, "dvc_conv2d: no tile configuration fits this geometry"),
+    ("conv2d", (1, 16, 64, 64, 32), dict(stride=2, dil=2, pad=2, cfg=0), {}, "dvc_conv2d: tile configuration 0 does not fit this geometry"),
+    ("conv2d", (1, 520, 8, 8, 32), {}, dict(in_scale=16, in_shift=16), "dvc_conv2d: fused input affine supports Cin <= 512"),
+    ("conv2d", (1, 24000, 8, 8, 64), dict(stride=2), dict(in_scale=16, in_shift=16), "dvc_conv2d: LDS tile too large ("),
+    ("winograd", _W, {}, dict(x=None), "dvc_conv2d_winograd: null argument"),
+    ("winograd", _W, dict(ksize=1, pad=0), {}, "dvc_conv2d_winograd: needs a 3x3 stride-1 layer with pad == dilation (1 or 2)"),
+    ("winograd", _W, dict(pad=2), {}, "dvc_conv2d_winograd: needs a 3x3 stride-1 layer with pad == dilation (1 or 2)"),
+    ("winograd", _W, dict(in_prelu=True), {}, "dvc_conv2d_winograd: no fused input transform on this path"),
+    ("winograd", _W, dict(in_sub=3), {}, "dvc_conv2d_winograd: bad in_up/in_sub"),
+    ("winograd", (0, 16, 8, 8, 64), {}, {}, "dvc_conv2d_winograd: bad shape"),
+    ("winograd", (1, 4, 8, 8, 64), {}, {}, "dvc_conv2d_winograd: needs Cin % 8 == 0 and Cout % 64 == 0 (got 4, 64)"),
+    ("winograd", _S, {}, {}, "dvc_conv2d_winograd: needs Cin % 8 == 0 and Cout % 64 == 0 (got 16, 32)"),
+    ("winograd", _W, {}, dict(w=20), "dvc_conv2d_winograd: weights must be 16-byte aligned"),
+    ("winograd", _BIG, {}, {}, "dvc_conv2d_winograd: tensor too large for buffer-descriptor staging"),
+    ("winograd", (1, 16, 1, 8, 64), dict(pad_mode=1), {}, "dvc_conv2d_winograd: reflect pad needs pad < input size"),
+    ("winograd", _W, dict(split_k=2), dict(ws=2 * 64 * 64 * 4 - 1),
+     "dvc_conv2d_winograd: split-K workspace too small for one image (split_k 2 needs 32768 bytes, got 32767)"),
+    ("winograd", _W, dict(cfg=0), {}, "dvc_conv2d_winograd: no configuration for cfg 0 / split_k 0 on this layer"),
+    ("winograd", _W, dict(split_k=3), dict(ws=1 << 20), "dvc_conv2d_winograd: no configuration for cfg -1 / split_k 3 on this layer"),
+    ("winograd", (1, 8, 2048, 2048, 64), dict(cfg=12, split_k=1), {},
+     "dvc_conv2d_winograd: 65536 workgroups per image (feature map too large for this path)"),
+    ("winograd", (5, 16, 8, 8, 64), dict(split_k=2, flags=1), dict(ws=2 * 2 * 64 * 64 * 4),
+     "dvc_conv2d_winograd: DVC_CONV_DEFER_REDUCE needs a workspace that holds the partial sums of the whole batch"),
+    ("winograd", _W, dict(split_k=2, flags=1), dict(ws=1 << 20, residual=16), "dvc_conv2d_winograd: DVC_CONV_DEFER_REDUCE does not carry a residual"),
+    ("pool", None, {}, {}, "dvc_conv2d_winograd_pool: null argument"),
+    ("pool", _W, {}, dict(y_pool=None), "dvc_conv2d_winograd_pool: null argument"),
+    ("pool", _W, dict(dil=2), {}, "dvc_conv2d_winograd_pool: dilation 1, no deferred reduce"),
+    ("pool", _W, dict(flags=1), {}, "dvc_conv2d_winograd_pool: dilation 1, no deferred reduce"),
+    ("pool", (1, 16, 1, 8, 64), {}, {}, "dvc_conv2d_winograd_pool: output smaller than a pooling window"),
+    ("pool", _W, {}, dict(x=None), "dvc_conv2d_winograd: null argument"),
+    ("pool", _S, {}, dict(y=None), "dvc_conv2d_winograd: needs Cin % 8 == 0 and Cout % 64 == 0 (got 16, 32)"),
+    ("dual", _W, {}, dict(x2=None), "dvc_conv2d_winograd_dual: null argument"),
+    ("dual", _W, {}, dict(d2=None), "dvc_conv2d_winograd_dual: null argument"),
+    ("dual", _W, {}, dict(d2=((2, 8, 8, 8, 64), {})), "dvc_conv2d_winograd_dual: the two convolutions must agree in batch"),
+    ("dual", _W, {}, dict(d2=((1, 8, 8, 8, 64), dict(dil=2))), "dvc_conv2d_winograd_dual: the two convolutions must agree in batch"),
+    ("dual", _W, {}, dict(d2=((1, 4, 8, 8, 64), {})), "dvc_conv2d_winograd_dual: both channel counts must be multiples of 8"),
+    ("dual", _W, {}, dict(d2=((1, 8, 8, 8, 64), dict(in_up=3))), "dvc_conv2d_winograd_dual: bad in_up/in_sub of the second input"),
+    ("dual", _W, dict(flags=1), dict(d2=((1, 8, 8, 8, 64), {})), "dvc_conv2d_winograd_dual: no deferred reduce on this entry"),
+    ("dual", _W, {}, dict(d2=((1, 8, 9, 8, 64), {})), "dvc_conv2d_winograd_dual: the two inputs' virtual sizes differ (8 x 8 vs 9 x 8)"),
+    ("dual", _W, dict(in_up=2), dict(d2=((1, 8, 8, 8, 64), {})), "dvc_conv2d_winograd_dual: the two inputs' virtual sizes differ (16 x 16 vs 8 x 8)"),
+    ("dual", (1, 8, 512, 512, 64), dict(in_up=2), dict(d2=((1, 512, 1024, 1024, 64), {})), "dvc_conv2d_winograd_dual: second input too large"),
+    ("dual", _W, dict(ksize=1, pad=0), dict(d2=((1, 8, 8, 8, 64), {})), "dvc_conv2d_winograd: needs a 3x3 stride-1 layer"),
+    ("group", [], {}, {}, "dvc_conv2d_winograd_group: 1..4 items"),
+    ("group", [(_W, {}, {})] * 5, {}, {}, "dvc_conv2d_winograd_group: 1..4 items"),
+    ("group", [(_W, {}, {}), (_W, {}, dict(x=None))], {}, {}, "dvc_conv2d_winograd_group: null argument in item 1"),
+    ("group", [(_W, {}, {}), (_W, {}, {})], {}, {}, "dvc_conv2d_winograd_group: items 0 and 1 share an output"),
+    ("group", [(_W, {}, {}), (_S, {}, dict(y=32))], {}, {}, "dvc_conv2d_winograd: needs Cin % 8 == 0 and Cout % 64 == 0 (got 16, 32)"),
+    ("group", [(_W, dict(split_k=2), dict(ws=1 << 20)), (_W, dict(split_k=2), dict(ws=1 << 20, y=32))], {}, {},
+     "dvc_conv2d_winograd_group: the split items 0 and 1 share a workspace"),
+    ("split", None, {}, {}, "dvc_conv2d_winograd_split: null argument"),
+    ("split", _W, dict(stride=2), {}, "dvc_conv2d_winograd: needs a 3x3 stride-1 layer with pad == dilation (1 or 2)"),
+    ("split", _W, dict(cfg=0), {}, "dvc_conv2d_winograd_split: no configuration for cfg 0 / split_k 0 on this layer"),
+]
+
+
+def _refusal_call(lib, entry, shape, fields, args):
+    """One row of CONV_REFUSALS as a C-ABI call; returns its return code."""
+    from dvc_amd import _lib, ops
+
+    def desc(shape, fields):
+        return None if shape is None else ctypes.byref(ops._conv_desc(*shape, **fields))
+
+    def p(name, default=16):
+        v = args.get(name, default)
+        return ctypes.c_void_p(v) if v else None
+
+    ws = args.get("ws", 0)
+    wsp = ctypes.c_void_p(4096) if ws else None
+    if entry == "conv2d":
+        return lib.dvc_conv2d(desc(shape, fields), p("x"), p("w"), None, p("in_scale", None), p("in_shift", None), None, None,
+                              p("residual", None), p("y"), wsp, ws, None)
+    if entry == "winograd":
+        return lib.dvc_conv2d_winograd(desc(shape, fields), p("x"), p("w"), None, None, p("residual", None), p("y"), wsp, ws, None)
+    if entry == "pool":
+        return lib.dvc_conv2d_winograd_pool(desc(shape, fields), p("x"), p("w"), None, None, p("y"), p("y_pool"), 0, wsp, ws, None)
+    if entry == "dual":
+        d2 = args.get("d2", ((1, 8, 8, 8, 64), {}))
+        return lib.dvc_conv2d_winograd_dual(desc(shape, fields), desc(*d2) if d2 else None, p("x"), p("x2"), p("w"), None, None, p("y"),
+                                            wsp, ws, None)
+    if entry == "split":
+        sp, ipl = ctypes.c_int32(0), ctypes.c_int32(0)
+        return lib.dvc_conv2d_winograd_split(desc(shape, fields), 1 << 20, ctypes.byref(sp) if shape else None, ctypes.byref(ipl))
+    assert entry == "group"
+    items = (_lib.DvcConvGroupItem * max(len(shape), 1))()
+    for it, (s, f, a) in zip(items, shape):
+        it.d = ops._conv_desc(*s, **f)
+        it.x, it.u_packed, it.y = a.get("x", 16), 16, a.get("y", 16)
+        it.workspace, it.workspace_bytes = (4096, a["ws"]) if a.get("ws") else (None, 0)
+    return lib.dvc_conv2d_winograd_group(items if shape else None, len(shape), None)
+
+
+@pytest.mark.parametrize("row", range(len(CONV_REFUSALS)), ids=lambda i: f"{CONV_REFUSALS[i][0]}-{i}")
+def test_conv_entry_points_refuse_before_any_launch(row):
+    """Host logic, no GPU: every DVC_REQUIRE of dvc_conv2d and of the Winograd entry points that fires before a launch, one bad
+    descriptor or argument per row, with the message it must produce (and, where two checks could fire, the one that does)."""
+    from dvc_amd import _lib
+    lib = _lib.load()
+    entry, shape, fields, args, message = CONV_REFUSALS[row]
+    rc = _refusal_call(lib, entry, shape, fields, args)
+    assert rc != 0 and message.encode() in lib.dvc_last_error(), lib.dvc_last_error()
+
+
 def test_winograd_reciprocal_decode_is_exact_below_65536():
     """csrc/conv_wino_kernel.h decodes the 1-D workgroup index with wino_div(n, wino_magic(d)) = umulhi(n, ceil(2^32 / d))
     (d == 1: magic 0, quotient n) for d = gx * gy, gx, blk_y * blk_x, blk_x and split, all of them <= the grid size.  Restated
