@@ -154,6 +154,12 @@ SIGNATURES = {
     "dvc_warp_slope_sum": (ctypes.c_int, [_VP, c_i64, _VP, _VP]),
     "dvc_warp_reflect_pad": (ctypes.c_int, [_VP, c_i32, c_i32, c_i32, _VP, _VP]),
     "dvc_warp_fold": (ctypes.c_int, [_VP, _VP, c_i32, c_i32, c_i32, _VP, _VP]),
+    "dvc_warp_head_wgrad_splits": (ctypes.c_int, [c_i32, c_i32, c_i32, c_i32, c_i32, c_i32]),
+    "dvc_warp_head_wgrad": (ctypes.c_int, [_VP, _VP, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, _VP, ctypes.c_size_t, _VP,
+                                           _VP]),
+    "dvc_warp_dilate_ring": (ctypes.c_int, [_VP, c_i32, c_i32, c_i32, c_i32, c_i32, _VP, _VP]),
+    "dvc_warp_up2_bwd": (ctypes.c_int, [_VP, c_i32, c_i32, c_i32, _VP, _VP]),
+    "dvc_warp_rpad_rows_bwd": (ctypes.c_int, [_VP, c_i32, c_i32, c_i32, c_i32, _VP, _VP]),
 }
 # diagnostics for tools/ (include/dvc_hip.h, last section): exported by the -DDVC_DEBUG build only
 DEBUG_SIGNATURES = {

@@ -14,7 +14,8 @@ losses need (train.py:649-668 take the perceptual and contextual losses on the f
 ColorVidNet in training mode (`colornet.train()`, grad mode on, the input or a parameter requiring grad) gives the gradients
 of all its parameters and of its input (train.py trains it).  WarpNet in training mode (`nonlocal_net.train()`, grad mode on, a
 parameter of layer.* / theta / phi requiring grad, the four heads frozen) gives the gradients of its residual trunk and of the
-theta / phi projections; its heads and its inputs carry no history.
+theta / phi projections; its heads and its inputs carry no history.  `nonlocal_net.set_head_training()` opts in to the heads'
+24 gradients as well: the four heads need not be frozen then, and only the inputs stay data.
 """
 import torch
 import torch.nn as nn
@@ -179,7 +180,8 @@ def _check_input(x, name):
             f"{name}: an input requires grad and autograd is enabled, but this forward is inference-only. Call it under "
             "torch.no_grad() as test.py:83 does, or detach the input; gradients exist for ColorVidNet in training mode "
             "(`colornet.train()`: parameters and input), WarpNet in training mode (`nonlocal_net.train()`: the residual trunk "
-            "and the theta / phi projections, heads frozen; its inputs are data), VGG19_pytorch.forward (input gradient, frozen "
+            "and the theta / phi projections, heads frozen — or all 43 parameters after `nonlocal_net.set_head_training()`; its "
+            "inputs are data), VGG19_pytorch.forward (input gradient, frozen "
             "weights), tensor_lab2rgb, the fused correlation (dvc_amd.corr_autograd) and the contextual losses.")
 
 
@@ -401,6 +403,29 @@ class _WarpTrain(torch.autograd.Function):
         return (dA, dB, None, None) + tuple(grads.get(n) for n in ctx.names)
 
 
+class _WarpHeadsTrain(torch.autograd.Function):
+    """WarpNet's four heads on both sides as one batch of 2N (WarpNet._heads_forward_saving), with what their backward needs
+    saved; backward takes the seam gradients (dA, dB) that _WarpTrain returns and gives the gradient of every head parameter
+    that requires grad (WarpNet._heads_backward).  The feature inputs are data."""
+
+    @staticmethod
+    def forward(ctx, module, names, feats, *params):
+        N = feats[0].shape[0]
+        need = {n for n, flag in zip(names, ctx.needs_input_grad[3:]) if flag}
+        saved = {}
+        trunk, rpad5 = module._heads_forward_saving([torch.cat((a, b), 0) for a, b in zip(feats[:4], feats[4:])], need, saved)
+        ctx.module, ctx.names, ctx.rpad5 = module, names, rpad5
+        _save_dict(ctx, saved)
+        return trunk[:N], trunk[N:]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dA, dB):
+        need = {n for n, flag in zip(ctx.names, ctx.needs_input_grad[3:]) if flag}
+        grads = ctx.module._heads_backward(_saved_dict(ctx), torch.cat((dA, dB), 0), need, ctx.rpad5)
+        return (None, None, None) + tuple(grads.get(n) for n in ctx.names)
+
+
 class _ResidualBlockParams(nn.Module):
     """Parameter container with the reference's names (conv1, conv2, prelu), NonlocalNet.py:330-339."""
 
@@ -563,11 +588,24 @@ class WarpNet(nn.Module):
     def _head_named_parameters(self):
         return [(n, p) for n, p in self.named_parameters() if n.split(".")[0] in self._HEADS]
 
+    @property
+    def head_training(self):
+        """Whether the training path also gives the 24 gradients of the four heads (set_head_training)."""
+        return self.__dict__.get("_head_training", False)
+
+    def set_head_training(self, flag=True):
+        """Opt in to (or out of) the heads' gradients: with it on, any of the 43 parameters requiring grad opens the training
+        path and backward fills every one of them that requires grad; with it off (the default) an unfrozen head is refused.
+        Not part of state_dict(); kept by pickling / copy.deepcopy.  Returns self."""
+        self.__dict__["_head_training"] = bool(flag)
+        return self
+
     def _takes_training_path(self):
-        return self.training and torch.is_grad_enabled() and any(p.requires_grad for _, p in self._trunk_named_parameters())
+        named = self.named_parameters() if self.head_training else self._trunk_named_parameters()
+        return self.training and torch.is_grad_enabled() and any(p.requires_grad for _, p in named)
 
     def _check_training_call(self, exemplar_cache, return_taps, defer_merge, detach_flag):
-        unfrozen = [n for n, p in self._head_named_parameters() if p.requires_grad]
+        unfrozen = [] if self.head_training else [n for n, p in self._head_named_parameters() if p.requires_grad]
         if unfrozen:
             raise NotImplementedError(
                 f"WarpNet: the training path gives the gradients of the residual trunk and the theta / phi projections only "
@@ -582,15 +620,21 @@ class WarpNet(nn.Module):
 
     def _forward_with_grad(self, ins, temperature, WTA_scale_weight):
         """(y, similarity_map) bit-identical to the no-grad forward on the fp32 correlation, with a backward to the trunk /
-        projection parameters.  The heads run as they do in inference, without history; the exemplar memo is neither read nor
-        filled."""
+        projection parameters.  The heads run as they do in inference, without history — or, after set_head_training with a head
+        parameter requiring grad, with history (_WarpHeadsTrain); the exemplar memo is neither read nor filled."""
         B_lab_map, A2, A3, A4, A5, B2, B3, B4, B5 = ins
         fh, fw = int(B_lab_map.shape[2] / 4), int(B_lab_map.shape[3] / 4)
-        _check_trainable(self._trunk_named_parameters(), "WarpNet")
+        heads = self._head_named_parameters() if self.head_training else []
+        _check_trainable(self._trunk_named_parameters() + heads, "WarpNet")
         with torch.no_grad():
-            trunkA = self._heads(A2, A3, A4, A5)
-            trunkB = self._heads(B2, B3, B4, B5)
             blab = ops.avgpool4x4(B_lab_map)
+        if any(p.requires_grad for _, p in heads):
+            # set_head_training: the heads run with history too, layer by layer, both sides as one batch
+            trunkA, trunkB = _WarpHeadsTrain.apply(self, tuple(n for n, _ in heads), tuple(ins[1:]), *(p for _, p in heads))
+        else:
+            with torch.no_grad():
+                trunkA = self._heads(A2, A3, A4, A5)
+                trunkB = self._heads(B2, B3, B4, B5)
         if (trunkA.shape[2], trunkA.shape[3]) != (fh, fw):
             raise RuntimeError(f"shape '[{B_lab_map.shape[0]}, 1, {fh}, {fw}]' is invalid for feature map "
                                f"of size {tuple(trunkA.shape[2:])}")
@@ -661,6 +705,101 @@ class WarpNet(nn.Module):
             g = ops.warp_fold(gp, skip=du)
             del gp, dz, du
         return g[:N], g[N:], grads
+
+    # ---- the heads with history (set_head_training): arch.WARP_HEAD_PLAN walked layer by layer, forward and backward
+    def _heads_forward_saving(self, feats, need, saved):
+        """The four heads on `feats` (relu2_1 .. relu5_1 of both sides as one batch) -> (the trunk tensor [2N,256,h,w], rpad5).
+        A head with a parameter in `need` runs site by site — conv, InstanceNorm, PReLU as launches of their own, the values of
+        the fused launches of _heads bit for bit (see _trunk) — and leaves in `saved`, under "<head>." + key: its input "x" and per
+        site the norm output "na" / "nb", its 1/sigma "ra" / "rb" and the first PReLU's output "pa".  Any other head keeps the
+        fused norm launches and saves nothing."""
+        M = feats[0].shape[0]
+        h, w, rpad5 = arch.warp_trunk_geometry([x.shape[2:] for x in feats])
+        trunk = torch.empty((M, arch.WARP_TRUNK_CH, h, w), device=feats[0].device, dtype=torch.float32)
+        bs = arch.WARP_TRUNK_CH * h * w
+
+        def stat(t):
+            return torch.empty(t.shape[0] * t.shape[1], device=t.device, dtype=torch.float32)
+
+        for hd in arch.WARP_HEAD_PLAN:
+            seq = getattr(self, hd.name)
+            ca, cb = seq[hd.conv_a], seq[hd.conv_b]
+            slope_a, slope_b = seq[hd.prelu_a].weight.detach(), seq[hd.prelu_b].weight.detach()
+            keep = any(n.startswith(hd.name + ".") for n in need)
+            rpad = rpad5 if hd.name == "layer5_1" else 0
+            out = trunk[:, hd.index * arch.WARP_FEATURE_CH:(hd.index + 1) * arch.WARP_FEATURE_CH]
+            x = feats[hd.index]
+            t = self._conv3(f"{hd.name}.{hd.conv_a}", ca, x, pad_mode=ops.PAD_REFLECT)
+            if keep:
+                ra = stat(t)
+                na = ops.instnorm_apply(t, out=t, scale_out=ra)
+                pa = ops.warp_prelu_fwd(na, slope_a)
+            else:
+                pa = ops.instnorm_apply(t, out=t, slope_t=slope_a)
+            in_up = 2 if hd.up_mid else 1
+            if hd.stride_b != 1:
+                t = ops.conv2d(pa, self._pk(f"{hd.name}.{hd.conv_b}", cb), cb.bias.detach(), stride=hd.stride_b,
+                               pad_mode=ops.PAD_REFLECT, in_up=in_up)
+            else:
+                t = self._conv3(f"{hd.name}.{hd.conv_b}", cb, pa, pad_mode=ops.PAD_REFLECT, in_up=in_up)
+            if not keep:
+                ops.instnorm_apply(t, slope_t=slope_b, up=2 if hd.up_out else 1, rpad=rpad, out=out, out_batch_stride=bs)
+                continue
+            rb = stat(t)
+            nb = ops.instnorm_apply(t, out=t, scale_out=rb)
+            pb = ops.warp_prelu_fwd(nb, slope_b)
+            if hd.up_out:
+                pb = ops.upsample_nearest(pb, 2)
+            out[:, :, rpad:h - rpad].copy_(pb)
+            if rpad:
+                out[:, :, :rpad].copy_(pb[:, :, :1])
+                out[:, :, h - rpad:].copy_(pb[:, :, -1:])
+            saved.update({f"{hd.name}.x": x, f"{hd.name}.na": na, f"{hd.name}.ra": ra, f"{hd.name}.pa": pa,
+                          f"{hd.name}.nb": nb, f"{hd.name}.rb": rb})
+        return trunk, rpad5
+
+    def _heads_backward(self, t, g_trunk, need, rpad5):
+        """Head parameter gradients (names in `need`) from the saved tensors `t` (_heads_forward_saving) and the gradient at
+        the trunk tensor of both sides g_trunk [2N,256,h,w].  Per head: its channel slice, the adjoints of the replicated rows and
+        of the x2 upsample, the second site's norm + PReLU backward, that convolution's weight gradient (dvc_warp_head_wgrad:
+        every head convolution, stride 1 or 2) and input gradient (W^T flipped on the forward's engines, a stride-2 layer's dz
+        spread by dvc_warp_dilate_ring first, then the fold), the adjoint of the inner upsample, the first site, the first
+        convolution's weight gradient.  The first convolution's input is data: no gradient.  A head with nothing in `need` is
+        skipped, and a head stops where nothing in front of it is wanted."""
+        grads = {}
+        for hd in arch.WARP_HEAD_PLAN:
+            pre = hd.name + "."
+            if not any(n.startswith(pre) for n in need):
+                continue
+            seq = getattr(self, hd.name)
+            ka, kb = f"{pre}{hd.conv_a}", f"{pre}{hd.conv_b}"
+            sa, sb = f"{pre}{hd.prelu_a}.weight", f"{pre}{hd.prelu_b}.weight"
+            g = g_trunk[:, hd.index * arch.WARP_FEATURE_CH:(hd.index + 1) * arch.WARP_FEATURE_CH].contiguous()
+            if hd.name == "layer5_1" and rpad5:
+                g = ops.warp_rpad_rows_bwd(g, rpad5)
+            if hd.up_out:
+                g = ops.warp_up2_bwd(g)
+            dz, _, sp = ops.warp_norm_prelu_bwd(g, t[pre + "nb"], t[pre + "rb"], seq[hd.prelu_b].weight.detach())
+            if sb in need:
+                grads[sb] = ops.warp_slope_sum(sp)
+            xb = ops.upsample_nearest(t[pre + "pa"], 2) if hd.up_mid else t[pre + "pa"]
+            if _wants(need, kb):
+                _put_wb(grads, need, kb, *ops.warp_head_wgrad(dz, ops.warp_reflect_pad(xb), stride=hd.stride_b))
+            if not (_wants(need, ka) or sa in need):
+                continue
+            if hd.stride_b == 2:
+                dz = ops.warp_dilate_ring(dz, xb.shape[2], xb.shape[3])
+            wt, packs = _bwd_filters(self._cache, "warp_bwd." + kb, seq[hd.conv_b].weight, vgg_bwd_weight)
+            g = ops.warp_fold(ops.conv3x3(dz, wt, packs, None, layer="warp_bwd." + kb))
+            del dz, xb
+            if hd.up_mid:
+                g = ops.warp_up2_bwd(g)
+            dz, _, sp = ops.warp_norm_prelu_bwd(g, t[pre + "na"], t[pre + "ra"], seq[hd.prelu_a].weight.detach())
+            if sa in need:
+                grads[sa] = ops.warp_slope_sum(sp)
+            if _wants(need, ka):
+                _put_wb(grads, need, ka, *ops.warp_head_wgrad(dz, ops.warp_reflect_pad(t[pre + "x"])))
+        return grads
 
     # ---- transparent exemplar memo (r05).  The reference's loop (test.py:68-96) hands the SAME exemplar tensors to every
     # frame_colorization call and NonlocalNet.py:452-465,473-476,491-493 recompute the exemplar side each time.  A caller that is

@@ -1582,3 +1582,59 @@ def warp_fold(g_padded, skip=None):
     dx = torch.empty((N, C, H, W), device=g_padded.device, dtype=torch.float32)
     _lib.check(lib.dvc_warp_fold(_p(g_padded), _p(skip), N * C, H, W, _p(dx), _stream()), "dvc_warp_fold")
     return dx
+
+
+# ---- WarpNet backward through the four heads (csrc/warp_head_bwd.hip; dvc_amd/nets.py walks arch.WARP_HEAD_PLAN)
+def warp_head_wgrad_splits(N, Cin, Cout, H, W, stride):
+    """The default number of position slots dvc_warp_head_wgrad splits a layer's sum over."""
+    return int(_lib.load().dvc_warp_head_wgrad_splits(N, Cin, Cout, H, W, stride))
+
+
+def warp_head_wgrad(dz_ringed, x_padded, *, stride=1, splits=None):
+    """dvc_warp_head_wgrad: (dW [Cout,Cin,3,3], db [Cout]) of a 3x3 reflect-pad-1 convolution of stride 1 or 2 from the
+    zero-ringed dz [N,Cout,Ho+2,Wo+2] (warp_norm_prelu_bwd) and the reflect-padded input [N,Cin,H+2,W+2] (warp_reflect_pad)."""
+    lib = _lib.load()
+    _need_all(dz_ringed=dz_ringed, x_padded=x_padded)
+    N, Cout = dz_ringed.shape[0], dz_ringed.shape[1]
+    Cin, H, W = x_padded.shape[1], x_padded.shape[2] - 2, x_padded.shape[3] - 2
+    if stride not in (1, 2) or H < 2 or W < 2 or x_padded.shape[0] != N or \
+            tuple(dz_ringed.shape[2:]) != ((H - 1) // stride + 3, (W - 1) // stride + 3):
+        raise RuntimeError(f"dvc_amd: warp_head_wgrad: dz_ringed {tuple(dz_ringed.shape)} is not the ringed stride-{stride} "
+                           f"output of x_padded {tuple(x_padded.shape)}")
+    S = warp_head_wgrad_splits(N, Cin, Cout, H, W, stride) if splits is None else int(splits)
+    return _slotted_wgrad("dvc_warp_head_wgrad", lambda part, out: lib.dvc_warp_head_wgrad(
+        _p(dz_ringed), _p(x_padded), N, Cin, Cout, H, W, stride, S, _p(part), part.numel(), _p(out), _stream()),
+        S, Cout, Cin, 3, dz_ringed.device)
+
+
+def warp_dilate_ring(dz_ringed, H, W):
+    """dvc_warp_dilate_ring: the zero-ringed dz [N,C,Ho+2,Wo+2] of a stride-2 layer on an H x W input -> [N,C,H+2,W+2], dz on the
+    odd rows / columns, zero elsewhere (what ops.conv3x3 with W^T flipped turns into the gradient at the padded input)."""
+    lib = _lib.load()
+    _need(dz_ringed, "dz_ringed")
+    N, C, Ho, Wo = dz_ringed.shape[0], dz_ringed.shape[1], dz_ringed.shape[2] - 2, dz_ringed.shape[3] - 2
+    out = torch.empty((N, C, H + 2, W + 2), device=dz_ringed.device, dtype=torch.float32)
+    _lib.check(lib.dvc_warp_dilate_ring(_p(dz_ringed), N * C, Ho, Wo, H, W, _p(out), _stream()), "dvc_warp_dilate_ring")
+    return out
+
+
+def warp_up2_bwd(g):
+    """dvc_warp_up2_bwd: the 2x2 block sums of g [N,C,2h,2w] -> [N,C,h,w] (backward of a x2 nearest upsample)."""
+    lib = _lib.load()
+    _need(g, "g")
+    N, C, H, W = g.shape
+    if H % 2 or W % 2:
+        raise RuntimeError(f"dvc_amd: warp_up2_bwd: {H} x {W} is not a x2 upsampled map")
+    out = torch.empty((N, C, H // 2, W // 2), device=g.device, dtype=torch.float32)
+    _lib.check(lib.dvc_warp_up2_bwd(_p(g), N * C, H // 2, W // 2, _p(out), _stream()), "dvc_warp_up2_bwd")
+    return out
+
+
+def warp_rpad_rows_bwd(g, rpad):
+    """dvc_warp_rpad_rows_bwd: backward of `rpad` replicated rows above and below: g [N,C,h+2*rpad,w] -> [N,C,h,w]."""
+    lib = _lib.load()
+    _need(g, "g")
+    N, C, PH, W = g.shape
+    out = torch.empty((N, C, PH - 2 * rpad, W), device=g.device, dtype=torch.float32)
+    _lib.check(lib.dvc_warp_rpad_rows_bwd(_p(g), N * C, PH - 2 * rpad, W, rpad, _p(out), _stream()), "dvc_warp_rpad_rows_bwd")
+    return out

@@ -655,6 +655,33 @@ int dvc_warp_slope_sum(const double* part, int64_t count, float* out, dvcStream 
 int dvc_warp_reflect_pad(const float* x, int32_t planes, int32_t H, int32_t W, float* x_padded, dvcStream stream);
 int dvc_warp_fold(const float* g_padded, const float* skip, int32_t planes, int32_t H, int32_t W, float* dx, dvcStream stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * WarpNet's backward through its four heads (training mode with WarpNet.set_head_training) — csrc/warp_head_bwd.hip.  The heads'
+ * norm + PReLU sites, 3x3 input gradients and reflect-pad adjoints run on the entry points above; these are what the heads add.
+ * Every sum has a fixed order: results are bit-deterministic.
+ *
+ * dvc_warp_head_wgrad:  weight and bias gradient of a 3x3 reflect-pad-1 convolution of stride s in {1, 2} on an H x W input
+ *   (H, W >= 2; output Ho x Wo, Ho = (H - 1) / s + 1), on v_mfma_f32_32x32x2_f32:
+ *   out[co][ci][ky][kx] = sum_{n,oy,ox} dz[n][co][oy][ox] x_padded[n][ci][s oy + ky][s ox + kx], then
+ *   out[Cout*Cin*9 + co] = sum dz[n][co] (in double).  dz_ringed [N][Cout][Ho+2][Wo+2] is the zero-ringed map
+ *   dvc_warp_norm_prelu_bwd writes (only its interior is read), x_padded [N][Cin][H+2][W+2] the output of dvc_warp_reflect_pad.
+ *   Only the Ho x Wo output positions are multiplied.  The positions are split over S slots (1 <= S <= 65535;
+ *   dvc_warp_head_wgrad_splits gives the default, 0 on bad sizes); part holds S * (Cout*Cin*9 + Cout) floats of partial sums,
+ *   added in slot order (in double) by a second launch.
+ * dvc_warp_dilate_ring:  out [planes][H+2][W+2] = 0 except out[1 + 2 oy][1 + 2 ox] = dz[oy][ox], dz the interior of
+ *   dz_ringed [planes][Ho+2][Wo+2] with Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1: the map whose zero-pad-1 3x3 convolution
+ *   with the transposed flipped filters is the gradient at the reflect-padded input of a stride-2 layer (then dvc_warp_fold).
+ * dvc_warp_up2_bwd:  out[planes][h][w] = the 2x2 block sums of g [planes][2h][2w] (backward of a x2 nearest upsample).
+ * dvc_warp_rpad_rows_bwd:  backward of rpad replicated rows above and below: out [planes][h][w] = rows rpad .. rpad+h-1 of
+ *   g [planes][h + 2 rpad][w], the rows above added onto row 0 and the rows below onto row h-1 (1 <= rpad <= 64). */
+int dvc_warp_head_wgrad_splits(int32_t N, int32_t Cin, int32_t Cout, int32_t H, int32_t W, int32_t stride);
+int dvc_warp_head_wgrad(const float* dz_ringed, const float* x_padded, int32_t N, int32_t Cin, int32_t Cout, int32_t H, int32_t W,
+                        int32_t stride, int32_t S, float* part, size_t part_floats, float* out, dvcStream stream);
+int dvc_warp_dilate_ring(const float* dz_ringed, int32_t planes, int32_t Ho, int32_t Wo, int32_t H, int32_t W, float* out,
+                         dvcStream stream);
+int dvc_warp_up2_bwd(const float* g, int32_t planes, int32_t h, int32_t w, float* out, dvcStream stream);
+int dvc_warp_rpad_rows_bwd(const float* g, int32_t planes, int32_t h, int32_t w, int32_t rpad, float* out, dvcStream stream);
+
 #ifdef DVC_DEBUG
 /* ------------------------------------------------------------------------------------------------
  * Diagnostics for the timing probes under tools/ — ONLY in a -DDVC_DEBUG build (`make -C csrc DEBUG=1` ->
