@@ -160,6 +160,16 @@ SIGNATURES = {
     "dvc_warp_dilate_ring": (ctypes.c_int, [_VP, c_i32, c_i32, c_i32, c_i32, c_i32, _VP, _VP]),
     "dvc_warp_up2_bwd": (ctypes.c_int, [_VP, c_i32, c_i32, c_i32, _VP, _VP]),
     "dvc_warp_rpad_rows_bwd": (ctypes.c_int, [_VP, c_i32, c_i32, c_i32, c_i32, _VP, _VP]),
+    "dvc_gan_spectral_sigma": (ctypes.c_int, [_VP, c_i32, c_i32, ctypes.c_float, _VP, _VP, _VP, _VP, ctypes.c_size_t, _VP]),
+    "dvc_gan_sn_weight": (ctypes.c_int, [_VP, _VP, c_i32, c_i32, _VP, _VP, c_i32, _VP]),
+    "dvc_gan_conv4s2": (ctypes.c_int, [ctypes.POINTER(DvcConvDesc), _VP, _VP, _VP, _VP, _VP, _VP]),
+    "dvc_gan_conv4s2_dgrad": (ctypes.c_int, [ctypes.POINTER(DvcConvDesc), _VP, _VP, _VP, _VP, _VP, _VP]),
+    "dvc_gan_last": (ctypes.c_int, [_VP, _VP, _VP, _VP, c_i32, c_i32, c_i32, c_i32, c_i64, _VP, _VP]),
+    "dvc_gan_last_bwd": (ctypes.c_int, [_VP, _VP, _VP, _VP, ctypes.c_float, c_i32, c_i32, c_i32, c_i32, _VP, _VP]),
+    "dvc_gan_softmax_rows": (ctypes.c_int, [_VP, c_i64, c_i32, _VP, _VP]),
+    "dvc_gan_softmax_rows_bwd": (ctypes.c_int, [_VP, _VP, c_i64, c_i32, _VP, _VP]),
+    "dvc_gan_scale_add": (ctypes.c_int, [_VP, _VP, _VP, c_i64, _VP, _VP]),
+    "dvc_gan_lrelu_bwd": (ctypes.c_int, [_VP, _VP, _VP, ctypes.c_float, c_i64, _VP, _VP]),
 }
 # diagnostics for tools/ (include/dvc_hip.h, last section): exported by the -DDVC_DEBUG build only
 DEBUG_SIGNATURES = {

@@ -280,3 +280,45 @@ def colorvidnet_param_shapes(ic=7):
 # are max 1.01, q99.9 0.90, mean 0.87, rms 0.88 of the CPU fp32 run's — the seven-layer map: 1.03 / 0.90 / 0.86 / 0.86 — for 25 us
 # per frame less; without conv3_2 as well q99.9 reaches 1.01 (mean 0.90), so that one stays.
 DIRECT_LAYERS = frozenset(("cvn.conv1_1.2", "cvn.conv1_2", "cvn.conv2_1", "cvn.conv2_2", "cvn.conv3_1", "cvn.conv3_2"))
+
+
+# ---------------------------------------------------------------------------------------------
+# Discriminator_x64 (models/GAN_models.py:104-157): six spectrally normalised 4x4 stride-2 pad-1 convolutions + LeakyReLU(0.2),
+# the self-attention block between layer4 and layer5, then the [3, 6] valid convolution `last` and the mean over its positions.
+GAN_LAYERS = ("layer1", "layer2", "layer3", "layer4", "layer5", "layer6")
+GAN_CH_MULT = (1, 1, 2, 4, 8, 16)            # Cout / ndf of layer1 .. layer6
+GAN_ATTENTION_AFTER = "layer4"
+GAN_ATTENTION_CONVS = ("query_conv", "key_conv", "value_conv")
+GAN_LAST_KSIZE = (3, 6)
+GAN_LRELU_SLOPE = 0.2
+GAN_SN_EPS = 1e-12
+
+
+def gan_conv_plan(in_size=6, ndf=64):
+    """[(name, cin, cout)] of layer1 .. layer6."""
+    chans = [in_size] + [m * ndf for m in GAN_CH_MULT]
+    return [(name, chans[i], chans[i + 1]) for i, name in enumerate(GAN_LAYERS)]
+
+
+def gan_out_hw(H, W):
+    """The map `last` sees: six halvings, each rounding down."""
+    for _ in GAN_LAYERS:
+        H, W = H // 2, W // 2
+    return H, W
+
+
+def discriminator_param_shapes(in_size=6, ndf=64):
+    """state_dict key -> shape, in the reference's order: per SpectralNorm module bias, weight_u, weight_v, weight_bar."""
+    def sn(prefix, cout, cin, kh, kw):
+        return {prefix + ".bias": (cout,), prefix + ".weight_u": (cout,), prefix + ".weight_v": (cin * kh * kw,),
+                prefix + ".weight_bar": (cout, cin, kh, kw)}
+    shapes = {}
+    plan = gan_conv_plan(in_size, ndf)
+    for name, cin, cout in plan:
+        shapes.update(sn(name + ".0.module", cout, cin, 4, 4))
+        if name == GAN_ATTENTION_AFTER:
+            shapes["attention.gamma"] = (1,)
+            for conv in GAN_ATTENTION_CONVS:
+                shapes.update(sn(f"attention.{conv}.module", cout, cout, 1, 1))
+    shapes.update(sn("last.module", 1, plan[-1][2], *GAN_LAST_KSIZE))
+    return shapes

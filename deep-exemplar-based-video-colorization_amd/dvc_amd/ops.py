@@ -1638,3 +1638,139 @@ def warp_rpad_rows_bwd(g, rpad):
     out = torch.empty((N, C, PH - 2 * rpad, W), device=g.device, dtype=torch.float32)
     _lib.check(lib.dvc_warp_rpad_rows_bwd(_p(g), N * C, PH - 2 * rpad, W, rpad, _p(out), _stream()), "dvc_warp_rpad_rows_bwd")
     return out
+
+
+# ---- Discriminator_x64, forward and input gradient (csrc/gan.hip; dvc_amd/gan.py walks the layers)
+def _gan_desc(N, Cin, H, W, Cout, *, slope, act, x_bs=0, y_bs=0):
+    return _conv_desc(N, Cin, H, W, Cout, ksize=4, stride=2, pad=1, act=act, act_slope=slope, x_batch_stride=x_bs,
+                      y_batch_stride=y_bs)
+
+
+def gan_spectral_sigma(w_bar, u, v, eps=1e-12):
+    """dvc_gan_spectral_sigma: one power step on w_bar [Cout, ...] read as [Cout, K]; u [Cout] and v [K] are updated IN PLACE.
+    Returns inv_sigma, a one-element device tensor holding 1 / (u^T W v) — nothing comes back to the host."""
+    lib = _lib.load()
+    _need_all(w_bar=w_bar, u=u, v=v)
+    Cout = w_bar.shape[0]
+    K = w_bar.numel() // Cout
+    assert u.numel() == Cout and v.numel() == K, (w_bar.shape, u.shape, v.shape)
+    inv = torch.empty(1, device=w_bar.device, dtype=torch.float32)
+    ws = _workspace(w_bar.device, (K + Cout) * 4, "gan_sn")
+    _lib.check(lib.dvc_gan_spectral_sigma(_p(w_bar), Cout, K, float(eps), _p(u), _p(v), _p(inv), _p(ws), ws.numel(), _stream()),
+               "dvc_gan_spectral_sigma")
+    return inv
+
+
+def gan_sn_weight(w_bar, inv_sigma, scaled=None, scaled_t=None, col=0):
+    """dvc_gan_sn_weight: w_bar [Cout, K] / sigma into `scaled` [Cout, K] and / or, transposed, into columns col .. col + Cout of
+    `scaled_t` [K, ld]."""
+    lib = _lib.load()
+    _need_all(w_bar=w_bar, inv_sigma=inv_sigma, scaled=scaled, scaled_t=scaled_t)
+    Cout = w_bar.shape[0]
+    K = w_bar.numel() // Cout
+    assert scaled is None or scaled.numel() == Cout * K, (scaled.shape, w_bar.shape)
+    ldt, pt = 0, None
+    if scaled_t is not None:
+        ldt = scaled_t.shape[1]
+        assert scaled_t.dim() == 2 and scaled_t.shape[0] == K and 0 <= col and col + Cout <= ldt, (scaled_t.shape, col, Cout)
+        pt = ctypes.c_void_p(scaled_t.data_ptr() + 4 * col)
+    _lib.check(lib.dvc_gan_sn_weight(_p(w_bar), _p(inv_sigma), Cout, K, _p(scaled), pt, ldt, _stream()), "dvc_gan_sn_weight")
+
+
+def gan_conv4s2(x, w_bar, bias, inv_sigma, *, act=ACT_LEAKY, slope=0.2, out=None, out_batch_stride=0):
+    """dvc_gan_conv4s2: act(conv 4x4 stride 2 zero-pad 1 (x, w_bar) / sigma + bias) -> [N, Cout, H // 2, W // 2]."""
+    lib = _lib.load()
+    _need_all(x=x, w_bar=w_bar, bias=bias, inv_sigma=inv_sigma)
+    N, Cin, H, W = x.shape
+    Cout = w_bar.shape[0]
+    assert tuple(w_bar.shape) == (Cout, Cin, 4, 4) and bias.numel() == Cout, (w_bar.shape, x.shape, bias.shape)
+    if out is None:
+        out = torch.empty((N, Cout, H // 2, W // 2), device=x.device, dtype=torch.float32)
+    d = _gan_desc(N, Cin, H, W, Cout, slope=slope, act=act, y_bs=out_batch_stride)
+    if conv_record is not None:
+        conv_record.append(_record_conv(d, affine=False, in_prelu=False, residual=False, algo="gan4s2"))
+    _lib.check(lib.dvc_gan_conv4s2(ctypes.byref(d), _p(x), _p(w_bar), _p(bias), _p(inv_sigma), _p(out), _stream()), "dvc_gan_conv4s2")
+    return out
+
+
+def gan_conv4s2_dgrad(dz, w_bar, inv_sigma, in_hw, *, mask_act=None, slope=0.2):
+    """dvc_gan_conv4s2_dgrad: the layer's input gradient [N, Cin, H, W] (in_hw = (H, W)) for dz [N, Cout, H // 2, W // 2], the
+    gradient at its pre-activation output; with mask_act (the layer's input, a LeakyReLU output) times that LeakyReLU's
+    derivative."""
+    lib = _lib.load()
+    _need_all(dz=dz, w_bar=w_bar, inv_sigma=inv_sigma, mask_act=mask_act)
+    (N, Cout, OH, OW), Cin, (H, W) = dz.shape, w_bar.shape[1], in_hw
+    assert tuple(w_bar.shape) == (Cout, Cin, 4, 4) and (OH, OW) == (H // 2, W // 2), (w_bar.shape, dz.shape, in_hw)
+    assert mask_act is None or tuple(mask_act.shape) == (N, Cin, H, W), (mask_act.shape, (N, Cin, H, W))
+    dx = torch.empty((N, Cin, H, W), device=dz.device, dtype=torch.float32)
+    d = _gan_desc(N, Cin, H, W, Cout, slope=slope, act=ACT_LEAKY)
+    _lib.check(lib.dvc_gan_conv4s2_dgrad(ctypes.byref(d), _p(dz), _p(w_bar), _p(inv_sigma), _p(mask_act), _p(dx), _stream()),
+               "dvc_gan_conv4s2_dgrad")
+    return dx
+
+
+def gan_last(x, w_bar, bias, inv_sigma):
+    """dvc_gan_last: mean over positions of conv [3, 6] valid (x, w_bar [1, Cin, 3, 6]) / sigma + bias -> [N, 1]."""
+    lib = _lib.load()
+    _need_all(x=x, w_bar=w_bar, bias=bias, inv_sigma=inv_sigma)
+    N, Cin, H, W = x.shape
+    assert tuple(w_bar.shape) == (1, Cin, 3, 6), (w_bar.shape, x.shape)
+    out = torch.empty((N, 1), device=x.device, dtype=torch.float32)
+    _lib.check(lib.dvc_gan_last(_p(x), _p(w_bar), _p(bias), _p(inv_sigma), N, Cin, H, W, 0, _p(out), _stream()), "dvc_gan_last")
+    return out
+
+
+def gan_last_bwd(g, w_bar, inv_sigma, x, *, mask=True, slope=0.2):
+    """dvc_gan_last_bwd: d loss / d x of gan_last for g [N, 1]; mask=True: times the derivative of the LeakyReLU that made x."""
+    lib = _lib.load()
+    _need_all(g=g, w_bar=w_bar, inv_sigma=inv_sigma, x=x)
+    N, Cin, H, W = x.shape
+    assert g.numel() == N and tuple(w_bar.shape) == (1, Cin, 3, 6), (g.shape, w_bar.shape, x.shape)
+    dx = torch.empty_like(x)
+    _lib.check(lib.dvc_gan_last_bwd(_p(g), _p(w_bar), _p(inv_sigma), _p(x) if mask else None, float(slope), N, Cin, H, W, _p(dx),
+                                    _stream()), "dvc_gan_last_bwd")
+    return dx
+
+
+def gan_softmax_rows(e, out=None):
+    """dvc_gan_softmax_rows: softmax over the last dimension with the row maximum subtracted; out may be e."""
+    lib = _lib.load()
+    _need_all(e=e, out=out)
+    if out is None:
+        out = torch.empty_like(e)
+    P = e.shape[-1]
+    _lib.check(lib.dvc_gan_softmax_rows(_p(e), e.numel() // P, P, _p(out), _stream()), "dvc_gan_softmax_rows")
+    return out
+
+
+def gan_softmax_rows_bwd(a, dA, out=None):
+    """dvc_gan_softmax_rows_bwd: a * (dA - sum_j a dA) over the last dimension; out may be dA."""
+    lib = _lib.load()
+    _need_all(a=a, dA=dA, out=out)
+    assert a.shape == dA.shape, (a.shape, dA.shape)
+    if out is None:
+        out = torch.empty_like(a)
+    P = a.shape[-1]
+    _lib.check(lib.dvc_gan_softmax_rows_bwd(_p(a), _p(dA), a.numel() // P, P, _p(out), _stream()), "dvc_gan_softmax_rows_bwd")
+    return out
+
+
+def gan_scale_add(o, gamma, x=None):
+    """dvc_gan_scale_add: gamma * o (+ x), gamma a one-element device tensor."""
+    lib = _lib.load()
+    _need_all(o=o, gamma=gamma, x=x)
+    assert x is None or x.shape == o.shape, (x.shape, o.shape)
+    y = torch.empty_like(o)
+    _lib.check(lib.dvc_gan_scale_add(_p(o), _p(x), _p(gamma), o.numel(), _p(y), _stream()), "dvc_gan_scale_add")
+    return y
+
+
+def gan_lrelu_bwd(d, g, act, slope=0.2):
+    """dvc_gan_lrelu_bwd: (d + g) * (act > 0 ? 1 : slope); d or g may be None (not both)."""
+    lib = _lib.load()
+    _need_all(d=d, g=g, act=act)
+    for t in (d, g):
+        assert t is None or t.shape == act.shape, (t.shape, act.shape)
+    out = torch.empty_like(act)
+    _lib.check(lib.dvc_gan_lrelu_bwd(_p(d), _p(g), _p(act), float(slope), act.numel(), _p(out), _stream()), "dvc_gan_lrelu_bwd")
+    return out

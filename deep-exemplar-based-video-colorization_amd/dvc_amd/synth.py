@@ -109,3 +109,24 @@ def synth_lab(seed, H=216, W=384):
 
 EXEMPLAR_SEED = 2
 FRAME_SEED0 = 1000
+
+
+def discriminator_state_dict(seed=0, ndf=64, in_size=6):
+    """Discriminator_x64 (dvc_amd.gan): He-uniform weight_bar, small biases, weight_u / weight_v drawn N(0, 1) and scaled to unit
+    length as the reference's SpectralNorm._make_params does, and attention.gamma = 0.5 — the module's own initial value is 0,
+    which would switch the attention block off."""
+    sd = {}
+    for key, shape in arch.discriminator_param_shapes(in_size, ndf).items():
+        g = _gen(seed + 3, key)
+        if key == "attention.gamma":
+            t = torch.full(shape, 0.5)
+        elif len(shape) == 4:
+            bound = math.sqrt(2.0) * math.sqrt(3.0 / (shape[1] * shape[2] * shape[3]))
+            t = (torch.rand(shape, generator=g) * 2 - 1) * bound
+        elif key.endswith(("weight_u", "weight_v")):
+            t = torch.randn(shape, generator=g)
+            t = t / (t.norm() + 1e-12)
+        else:
+            t = (torch.rand(shape, generator=g) * 2 - 1) * 0.05
+        sd[key] = t.float()
+    return sd

@@ -70,7 +70,7 @@ enum { DVC_PAD_ZERO = 0, DVC_PAD_REFLECT = 1 };
 typedef struct DvcConvDesc {
     int32_t N, Cin, H, W;       /* stored input tensor */
     int32_t Cout;
-    int32_t ksize;              /* 1 or 3 */
+    int32_t ksize;              /* 1 or 3 (4: dvc_gan_conv4s2 / _dgrad only) */
     int32_t stride;             /* 1 or 2 */
     int32_t dil;                /* 1 or 2 */
     int32_t pad;                /* 0..2 */
@@ -681,6 +681,51 @@ int dvc_warp_dilate_ring(const float* dz_ringed, int32_t planes, int32_t Ho, int
                          dvcStream stream);
 int dvc_warp_up2_bwd(const float* g, int32_t planes, int32_t h, int32_t w, float* out, dvcStream stream);
 int dvc_warp_rpad_rows_bwd(const float* g, int32_t planes, int32_t h, int32_t w, int32_t rpad, float* out, dvcStream stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Discriminator_x64 as a frozen critic (models/GAN_models.py:104-157, models/spectral_normalization.py): forward and the
+ * gradient back to its input — csrc/gan.hip, walked by dvc_amd/gan.py.  Every sum has a fixed order and nothing is added
+ * atomically: results are bit-deterministic.  W_bar is the stored filter [Cout][Cin][kh][kw], read as the matrix [Cout][K]; it
+ * is never rewritten: each layer multiplies by the device scalar inv_sigma[0] = 1 / sigma in its epilogue.
+ *
+ * dvc_gan_spectral_sigma:  one power step of SpectralNorm on W_bar [Cout][K] (1 <= Cout, K):  v <- l2n(W_bar^T u),
+ *   u <- l2n(W_bar v), l2n(z) = z / (|z| + eps), then inv_sigma[0] = 1 / (u^T W_bar v).  u [Cout] and v [K] are updated in place.
+ *   workspace: at least (K + Cout) floats.  Three launches.
+ * dvc_gan_sn_weight:  w_scaled[co][k] = W_bar[co][k] * inv_sigma[0] and (when w_scaled_t != NULL) w_scaled_t[k * ldt + co] the
+ *   same, transposed: the filters of the attention block's 1x1 projections in the two layouts dvc_conv2d (ksize 1) takes for the
+ *   forward and the input gradient; ldt >= Cout lets three projections share one stacked matrix.  w_scaled may be NULL.
+ * dvc_gan_conv4s2:  y = act(conv4x4, stride 2, zero pad 1 (x, W_bar) * inv_sigma[0] + bias) as an implicit GEMM over K = 16 Cin
+ *   on v_mfma_f32_32x32x2_f32.  d: N, Cin, H, W, Cout, ksize 4, stride 2, pad 1, dil 1, act NONE or LEAKY (act_slope), the batch
+ *   strides of x and y; every other field at its default.  Output OH x OW = H / 2 x W / 2 (floor); H, W >= 2, any Cout >= 1.
+ *   W_bar 16-byte aligned.
+ * dvc_gan_conv4s2_dgrad:  the input gradient of that layer in gather form, d describing the FORWARD layer:
+ *   dx[n][ci][iy][ix] = inv_sigma[0] * sum_{co} sum_{2x2 taps by the parity of iy, ix} W_bar[co][ci][ky][kx] dz[n][co][oy][ox],
+ *   dz [N][Cout][OH][OW] (batch stride d->y_batch_stride) the gradient at the layer's PRE-activation output, dx [N][Cin][H][W]
+ *   (batch stride d->x_batch_stride).  mask_act != NULL ([N][Cin][H][W], dense — the layer's input, i.e. the LeakyReLU output of
+ *   the layer in front): dx is multiplied by (mask_act > 0 ? 1 : d->act_slope), which makes it the dz of that layer.
+ * dvc_gan_last / dvc_gan_last_bwd:  out[n] = mean over the (H-2) x (W-5) positions of conv [3,6] valid (x, W_bar [1][Cin][3][6])
+ *   * inv_sigma[0] + bias[0], x [N][Cin][H][W] with H >= 3, W >= 6; and its input gradient for g [N] = d loss / d out, times
+ *   (mask_act > 0 ? 1 : slope) when mask_act != NULL (x itself, the LeakyReLU output of the layer in front).
+ * dvc_gan_softmax_rows:  a[r][j] = exp(e[r][j] - max_j e[r]) / sum_j exp(...) for `rows` rows of P floats; a may be e.
+ * dvc_gan_softmax_rows_bwd:  dE[r][j] = a[r][j] (dA[r][j] - sum_j a[r][j] dA[r][j]); dE may be dA.
+ * dvc_gan_scale_add:  y[i] = gamma[0] * o[i] + x[i] (x == NULL: gamma[0] * o[i]) for count floats; gamma on the device.
+ * dvc_gan_lrelu_bwd:  out[i] = (d[i] + g[i]) * (act[i] > 0 ? 1 : slope); d or g may be NULL (not both); out may be d or g. */
+int dvc_gan_spectral_sigma(const float* w_bar, int32_t Cout, int32_t K, float eps, float* u, float* v, float* inv_sigma,
+                           void* workspace, size_t workspace_bytes, dvcStream stream);
+int dvc_gan_sn_weight(const float* w_bar, const float* inv_sigma, int32_t Cout, int32_t K, float* w_scaled, float* w_scaled_t,
+                      int32_t ldt, dvcStream stream);
+int dvc_gan_conv4s2(const DvcConvDesc* d, const float* x, const float* w_bar, const float* bias, const float* inv_sigma, float* y,
+                    dvcStream stream);
+int dvc_gan_conv4s2_dgrad(const DvcConvDesc* d, const float* dz, const float* w_bar, const float* inv_sigma,
+                          const float* mask_act, float* dx, dvcStream stream);
+int dvc_gan_last(const float* x, const float* w_bar, const float* bias, const float* inv_sigma, int32_t N, int32_t Cin, int32_t H,
+                 int32_t W, int64_t x_batch_stride, float* out, dvcStream stream);
+int dvc_gan_last_bwd(const float* g, const float* w_bar, const float* inv_sigma, const float* mask_act, float slope, int32_t N,
+                     int32_t Cin, int32_t H, int32_t W, float* dx, dvcStream stream);
+int dvc_gan_softmax_rows(const float* e, int64_t rows, int32_t P, float* a, dvcStream stream);
+int dvc_gan_softmax_rows_bwd(const float* a, const float* dA, int64_t rows, int32_t P, float* dE, dvcStream stream);
+int dvc_gan_scale_add(const float* o, const float* x, const float* gamma, int64_t count, float* y, dvcStream stream);
+int dvc_gan_lrelu_bwd(const float* d, const float* g, const float* act, float slope, int64_t count, float* out, dvcStream stream);
 
 #ifdef DVC_DEBUG
 /* ------------------------------------------------------------------------------------------------
