@@ -170,6 +170,12 @@ SIGNATURES = {
     "dvc_gan_softmax_rows_bwd": (ctypes.c_int, [_VP, _VP, c_i64, c_i32, _VP, _VP]),
     "dvc_gan_scale_add": (ctypes.c_int, [_VP, _VP, _VP, c_i64, _VP, _VP]),
     "dvc_gan_lrelu_bwd": (ctypes.c_int, [_VP, _VP, _VP, ctypes.c_float, c_i64, _VP, _VP]),
+    "dvc_gan_conv4s2_wgrad_splits": (ctypes.c_int, [ctypes.POINTER(DvcConvDesc)]),
+    "dvc_gan_conv4s2_wgrad": (ctypes.c_int, [ctypes.POINTER(DvcConvDesc), _VP, _VP, c_i32, _VP, ctypes.c_size_t, _VP, _VP]),
+    "dvc_gan_dot_workspace_bytes": (ctypes.c_size_t, [c_i64]),
+    "dvc_gan_sn_wgrad": (ctypes.c_int, [_VP, _VP, _VP, _VP, _VP, c_i32, c_i32, _VP, _VP, ctypes.c_size_t, _VP]),
+    "dvc_gan_last_wgrad": (ctypes.c_int, [_VP, _VP, c_i32, c_i32, c_i32, c_i32, c_i64, _VP, _VP]),
+    "dvc_gan_dot": (ctypes.c_int, [_VP, _VP, c_i64, _VP, _VP, ctypes.c_size_t, _VP]),
 }
 # diagnostics for tools/ (include/dvc_hip.h, last section): exported by the -DDVC_DEBUG build only
 DEBUG_SIGNATURES = {

@@ -1774,3 +1774,67 @@ def gan_lrelu_bwd(d, g, act, slope=0.2):
     out = torch.empty_like(act)
     _lib.check(lib.dvc_gan_lrelu_bwd(_p(d), _p(g), _p(act), float(slope), act.numel(), _p(out), _stream()), "dvc_gan_lrelu_bwd")
     return out
+
+
+# ---- Discriminator_x64, parameter gradients (csrc/gan_wgrad.hip; dvc_amd/gan.py launches them behind set_parameter_training)
+def gan_conv4s2_wgrad_splits(N, Cin, H, W, Cout):
+    """The default number of pixel slots dvc_gan_conv4s2_wgrad splits a layer's sum over."""
+    d = _gan_desc(N, Cin, H, W, Cout, slope=0.2, act=ACT_LEAKY)
+    return int(_lib.load().dvc_gan_conv4s2_wgrad_splits(ctypes.byref(d)))
+
+
+def gan_conv4s2_wgrad(dz, x, *, splits=None):
+    """dvc_gan_conv4s2_wgrad: (G [Cout, Cin, 4, 4], db [Cout]), the plain weight gradient and the bias gradient of a 4x4 stride-2
+    pad-1 layer from dz [N, Cout, H // 2, W // 2], the gradient at its pre-activation, and its input x [N, Cin, H, W]."""
+    lib = _lib.load()
+    _need_all(dz=dz, x=x)
+    (N, Cout, OH, OW), (Cin, H, W) = dz.shape, x.shape[1:]
+    assert x.shape[0] == N and (OH, OW) == (H // 2, W // 2), (dz.shape, x.shape)
+    d = _gan_desc(N, Cin, H, W, Cout, slope=0.2, act=ACT_LEAKY)
+    S = int(lib.dvc_gan_conv4s2_wgrad_splits(ctypes.byref(d))) if splits is None else int(splits)
+    return _slotted_wgrad("dvc_gan_conv4s2_wgrad", lambda part, out: lib.dvc_gan_conv4s2_wgrad(
+        ctypes.byref(d), _p(dz), _p(x), S, _p(part), part.numel(), _p(out), _stream()), S, Cout, Cin, 4, dz.device)
+
+
+def _gan_dot_workspace(device, count):
+    return _workspace(device, int(_lib.load().dvc_gan_dot_workspace_bytes(count)), "gan_dot")
+
+
+def gan_sn_wgrad(G, w_bar, u, v, inv_sigma, out=None):
+    """dvc_gan_sn_wgrad: d loss / d w_bar = (G - <G, w_bar> / sigma * u v^T) / sigma in w_bar's shape, for the plain weight
+    gradient G and the vectors u [Cout], v [K] the forward's power step left.  `out` (a contiguous tensor of that shape) is
+    overwritten."""
+    lib = _lib.load()
+    _need_all(G=G, w_bar=w_bar, u=u, v=v, inv_sigma=inv_sigma, out=out)
+    Cout = w_bar.shape[0]
+    K = w_bar.numel() // Cout
+    assert G.numel() == Cout * K and u.numel() == Cout and v.numel() == K and inv_sigma.numel() == 1, (G.shape, w_bar.shape, u.shape, v.shape)
+    if out is None:
+        out = torch.empty_like(w_bar)
+    assert out.shape == w_bar.shape, (out.shape, w_bar.shape)
+    ws = _gan_dot_workspace(G.device, Cout * K)
+    _lib.check(lib.dvc_gan_sn_wgrad(_p(G), _p(w_bar), _p(u), _p(v), _p(inv_sigma), Cout, K, _p(out), _p(ws), ws.numel(), _stream()),
+               "dvc_gan_sn_wgrad")
+    return out
+
+
+def gan_last_wgrad(g, x):
+    """dvc_gan_last_wgrad: (G [1, Cin, 3, 6], db [1]) of gan_last on x [N, Cin, H, W] for g [N, 1] = d loss / d out."""
+    lib = _lib.load()
+    _need_all(g=g, x=x)
+    N, Cin, H, W = x.shape
+    assert g.numel() == N, (g.shape, x.shape)
+    out = torch.empty(Cin * 18 + 1, device=x.device, dtype=torch.float32)
+    _lib.check(lib.dvc_gan_last_wgrad(_p(g), _p(x), N, Cin, H, W, 0, _p(out), _stream()), "dvc_gan_last_wgrad")
+    return out[:Cin * 18].view(1, Cin, 3, 6), out[Cin * 18:]
+
+
+def gan_dot(a, b):
+    """dvc_gan_dot: sum(a * b) in double in a fixed order, rounded once -> a one-element tensor."""
+    lib = _lib.load()
+    _need_all(a=a, b=b)
+    assert a.numel() == b.numel(), (a.shape, b.shape)
+    out = torch.empty(1, device=a.device, dtype=torch.float32)
+    ws = _gan_dot_workspace(a.device, a.numel())
+    _lib.check(lib.dvc_gan_dot(_p(a), _p(b), a.numel(), _p(out), _p(ws), ws.numel(), _stream()), "dvc_gan_dot")
+    return out

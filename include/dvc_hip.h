@@ -727,6 +727,40 @@ int dvc_gan_softmax_rows_bwd(const float* a, const float* dA, int64_t rows, int3
 int dvc_gan_scale_add(const float* o, const float* x, const float* gamma, int64_t count, float* y, dvcStream stream);
 int dvc_gan_lrelu_bwd(const float* d, const float* g, const float* act, float slope, int64_t count, float* out, dvcStream stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Discriminator_x64: its own parameter gradients — csrc/gan_wgrad.hip, launched by dvc_amd/gan.py behind
+ * `set_parameter_training()`.  SpectralNorm computes sigma = u'^T W_bar v' inside the graph with the vectors u', v' the power step
+ * of THAT forward left (constants), and the layer uses W = W_bar / sigma; so with G = d loss / d W, the plain weight gradient,
+ * d loss / d W_bar = G / sigma - (<G, W_bar> / sigma^2) u' v'^T.  Fixed orders, no atomics: bit-deterministic.
+ *
+ * dvc_gan_conv4s2_wgrad:  G and the bias gradient of the layer d describes (the fields dvc_gan_conv4s2 reads; act is not used):
+ *   out[((co Cin + ci) 4 + ky) 4 + kx] = sum_{n,oy,ox} dz[n][co][oy][ox] x[n][ci][2 oy + ky - 1][2 ox + kx - 1] (out of range: 0),
+ *   then out[Cout Cin 16 + co] = sum_{n,oy,ox} dz[n][co][oy][ox] (a double chain per slot).  dz [N][Cout][OH][OW] (batch stride
+ *   d->y_batch_stride) is the gradient at the layer's PRE-activation output, x [N][Cin][H][W] (d->x_batch_stride) its input.
+ *   On v_mfma_f32_32x32x2_f32; the pixels, numbered over the whole batch, are cut into chunks of 16 and the chunks into S
+ *   contiguous ranges, 1 <= S <= 65535 (dvc_gan_conv4s2_wgrad_splits(d): the default; 0 for a descriptor that is refused).  part:
+ *   S slots of ld = Cout Cin 16 + Cout floats (part_floats >= S ld), every float of which is written; out [ld] = the slots added
+ *   in slot order in double, rounded once.  The bits depend on S and on nothing else.  out and part alias neither each other nor
+ *   an input.  Two launches.
+ * dvc_gan_sn_wgrad:  out[co][k] = (G[co][k] - c u[co] v[k]) * inv_sigma[0] with c = <G, W_bar> * inv_sigma[0], the inner product
+ *   in double in a fixed order, every element computed in double and rounded once.  G, W_bar, out [Cout][K]; u [Cout], v [K] the
+ *   vectors AFTER the forward's power step.  out is overwritten (accumulating into a .grad is the caller's business) and aliases
+ *   no input.  workspace: dvc_gan_dot_workspace_bytes(Cout K) bytes, 8-byte aligned.  Two launches.
+ * dvc_gan_last_wgrad:  for `last` (dvc_gan_last) on x [N][Cin][H][W], H >= 3, W >= 6, and g [N] = d loss / d out:
+ *   out[(c 3 + ky) 6 + kx] = sum_n g[n] / cnt * sum_{oy,ox} x[n][c][oy + ky][ox + kx], cnt = (H-2)(W-5); out[Cin 18] = sum_n g[n].
+ * dvc_gan_dot:  out[0] = sum_i a[i] b[i] over count >= 1 floats, in double in a fixed order that depends on count alone, rounded
+ *   once.  workspace as for dvc_gan_sn_wgrad.  Two launches. */
+int dvc_gan_conv4s2_wgrad_splits(const DvcConvDesc* d);
+int dvc_gan_conv4s2_wgrad(const DvcConvDesc* d, const float* dz, const float* x, int32_t S, float* part, size_t part_floats,
+                          float* out, dvcStream stream);
+size_t dvc_gan_dot_workspace_bytes(int64_t count);
+int dvc_gan_sn_wgrad(const float* G, const float* w_bar, const float* u, const float* v, const float* inv_sigma, int32_t Cout,
+                     int32_t K, float* out, void* workspace, size_t workspace_bytes, dvcStream stream);
+int dvc_gan_last_wgrad(const float* g, const float* x, int32_t N, int32_t Cin, int32_t H, int32_t W, int64_t x_batch_stride,
+                       float* out, dvcStream stream);
+int dvc_gan_dot(const float* a, const float* b, int64_t count, float* out, void* workspace, size_t workspace_bytes,
+                dvcStream stream);
+
 #ifdef DVC_DEBUG
 /* ------------------------------------------------------------------------------------------------
  * Diagnostics for the timing probes under tools/ — ONLY in a -DDVC_DEBUG build (`make -C csrc DEBUG=1` ->
