@@ -317,17 +317,39 @@ static int conv_plan(const DvcConvDesc* d, int OH, int OW, bool affine, bool hav
         // (32x32 MFMA tiles per wave, padding included) x (waves per SIMD, at least one round) x a
         // staging penalty that grows as the tile shrinks (more staged bytes per MFMA).
         static const double pen[5] = {1.00, 1.06, 1.06, 1.12, 1.35};
-        double best = 1e30;
-        for (int i = 0; i < 5; ++i) {
-            if (!conv_cfg_fits(d, p.tw, gen, i)) continue;
-            const ConvCfg& c = kConvCfgs[i];
-            int mt = 32 * c.wm * c.rm, ph = c.wn * c.rn * (32 / p.tw);
-            if (d->Cout < mt && i != 1 && i != 3) continue;  // don't waste half the M tile
-            double waves = 4.0 * cdiv(OW, p.tw) * cdiv(OH, ph) * cdiv(d->Cout, mt);     // of one image
-            double rounds = waves / 1024.0;
-            double pn = (i == 4 && rounds <= 1.0) ? 1.10 : pen[i];
-            double cost = c.rm * c.rn * (rounds < 1.0 ? 1.0 : rounds) * pn;
-            if (cost < best) { best = cost; cfg = i; }
+        auto choose = [&](int tw, bool any_mt) {
+            int pick = -1;
+            double best = 1e30;
+            for (int i = 0; i < 5; ++i) {
+                if (!conv_cfg_fits(d, tw, gen, i)) continue;
+                const ConvCfg& c = kConvCfgs[i];
+                int mt = 32 * c.wm * c.rm, ph = c.wn * c.rn * (32 / tw);
+                if (!any_mt && d->Cout < mt && i != 1 && i != 3) continue;  // don't waste half the M tile
+                double waves = 4.0 * cdiv(OW, tw) * cdiv(OH, ph) * cdiv(d->Cout, mt);     // of one image
+                double rounds = waves / 1024.0;
+                double pn = (i == 4 && rounds <= 1.0) ? 1.10 : pen[i];
+                double cost = c.rm * c.rn * (rounds < 1.0 ? 1.0 : rounds) * pn;
+                if (cost < best) { best = cost; pick = i; }
+            }
+            return pick;
+        };
+        cfg = choose(p.tw, false);
+        // The run-time-geometry (stride-2) kernel stages so little per thread that often only configuration 4 fits, and at a
+        // 16-wide tile with dilation 2 none does.  A legal layer is never refused for that: first the 64-channel tile for a layer
+        // with fewer output channels, then the other tile widths, narrowest padding first.  (Every layer the rules above take
+        // keeps its plan.)
+        if (cfg < 0) cfg = choose(p.tw, true);
+        int widths[3] = {32, 16, 8};
+        std::sort(widths, widths + 3, [&](int a, int b) {
+            const int wa = cdiv(OW, a) * a, wb = cdiv(OW, b) * b;
+            return wa != wb ? wa < wb : a > b;      // (pick_tw's order: its own choice comes first)
+        });
+        for (int tw : widths) {
+            if (cfg >= 0) break;
+            if (tw == p.tw) continue;
+            cfg = choose(tw, false);
+            if (cfg < 0) cfg = choose(tw, true);
+            if (cfg >= 0) p.tw = tw;
         }
         DVC_REQUIRE(cfg >= 0, "dvc_conv2d: no tile configuration fits this geometry");
     }

@@ -107,7 +107,7 @@ def _norm_feats(sd_v, lab, dtype=torch.float32):
     return [O.feature_normalize(t) for t in f[1:]]
 
 
-@pytest.mark.parametrize("H,W", [(48, 80), (40, 64), (216, 384)])
+@pytest.mark.parametrize("H,W", [(48, 80), (40, 64), (216, 384), (64, 96), (96, 160)])   # (the last two: stage 3 of the heads is a mixed Winograd / direct group)
 def test_warpnet_stages_identical_inputs(nets, weights, H, W):
     """heads+trunk, theta/phi projection and the fused correlation, each on identical inputs."""
     from dvc_amd import synth
@@ -180,12 +180,13 @@ def test_vgg_gray_input_folded_into_conv1_1_is_bit_identical(nets, H, W, N):
             assert torch.equal(a, b)
 
 
-@pytest.mark.parametrize("H,W,N", [(216, 384, 1), (48, 80, 2), (40, 64, 1), (432, 768, 1)])
+@pytest.mark.parametrize("H,W,N", [(216, 384, 1), (48, 80, 2), (40, 64, 1), (432, 768, 1), (64, 96, 1), (96, 160, 2)])
 def test_warpnet_heads_grouped_launches_are_bit_identical(nets, weights, H, W, N):
     """r06: the four heads advance stage by stage, each stage ONE launch over the independent layers
     (dvc_conv2d_winograd_group / dvc_instnorm_apply_group).  Every item keeps the plan and the kernel body it has as a launch
     of its own, so heads + trunk must come out bit-identical with DVC_GROUP_HEADS on and off — at the path's size, a batch, the
-    replicate-pad geometry (40x64) and configs[3]'s size; and the grouped form really is fewer launches."""
+    replicate-pad geometry (40x64) and configs[3]'s size; and the grouped form really is fewer launches.  At 64x96 and 96x160 stage 3
+    is a mixed Winograd / direct group: conv3x3_group takes its per-layer fall-back with the per-item workspaces conv.g{i}."""
     from dvc_amd import _lib, ops, synth
     warp = nets[1]
     sd_v = weights[0]
