@@ -47,6 +47,19 @@ class DvcInstNormItem(ctypes.Structure):
     ]
 
 
+class DvcAdamTensor(ctypes.Structure):
+    _fields_ = [
+        ("p", ctypes.c_void_p), ("g", ctypes.c_void_p), ("m", ctypes.c_void_p), ("v", ctypes.c_void_p), ("vmax", ctypes.c_void_p),
+        ("n", c_i64), ("step_size", ctypes.c_float), ("inv_sqrt_bc2", ctypes.c_float), ("beta2", ctypes.c_float),
+        ("one_minus_beta1", ctypes.c_float), ("one_minus_beta2", ctypes.c_float), ("eps", ctypes.c_float),
+        ("weight_decay", ctypes.c_float), ("reserved", ctypes.c_float),
+    ]
+
+
+class DvcAdamChunk(ctypes.Structure):
+    _fields_ = [("tensor", c_i32), ("reserved", c_i32), ("start", c_i64)]
+
+
 # every symbol include/dvc_hip.h declares: name -> (restype, argtypes)
 _VP = ctypes.c_void_p
 SIGNATURES = {
@@ -176,6 +189,7 @@ SIGNATURES = {
     "dvc_gan_sn_wgrad": (ctypes.c_int, [_VP, _VP, _VP, _VP, _VP, c_i32, c_i32, _VP, _VP, ctypes.c_size_t, _VP]),
     "dvc_gan_last_wgrad": (ctypes.c_int, [_VP, _VP, c_i32, c_i32, c_i32, c_i32, c_i64, _VP, _VP]),
     "dvc_gan_dot": (ctypes.c_int, [_VP, _VP, c_i64, _VP, _VP, ctypes.c_size_t, _VP]),
+    "dvc_adam_step": (ctypes.c_int, [_VP, c_i32, _VP, c_i64, _VP]),
 }
 # diagnostics for tools/ (include/dvc_hip.h, last section): exported by the -DDVC_DEBUG build only
 DEBUG_SIGNATURES = {

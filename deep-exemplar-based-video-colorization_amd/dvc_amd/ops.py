@@ -1838,3 +1838,22 @@ def gan_dot(a, b):
     ws = _gan_dot_workspace(a.device, a.numel())
     _lib.check(lib.dvc_gan_dot(_p(a), _p(b), a.numel(), _p(out), _p(ws), ws.numel(), _stream()), "dvc_gan_dot")
     return out
+
+
+# ---- the optimiser step (csrc/optim.hip; dvc_amd/optim.py fills the tables)
+def _need_table(t, name, nbytes):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError(f"dvc_amd: `{name}` must be a ROCm device tensor; the HIP path has no CPU fallback")
+    if t.dtype != torch.uint8 or not t.is_contiguous() or t.numel() < nbytes or t.data_ptr() % 8:
+        raise RuntimeError(f"dvc_amd: `{name}` must be a contiguous 8-byte aligned uint8 tensor of at least {nbytes} bytes")
+    if t.device.index != _current_device():
+        raise RuntimeError(f"dvc_amd: `{name}` lives on {t.device} but the current device is cuda:{_current_device()}")
+
+
+def adam_step(tensor_table, n_tensors, chunk_table, n_chunks):
+    """dvc_adam_step: ONE launch that applies Adam to every tensor of the two device-resident tables — uint8 device tensors that
+    hold n_tensors DvcAdamTensor and n_chunks DvcAdamChunk records (dvc_amd.optim.build_tables lays them out)."""
+    lib = _lib.load()
+    _need_table(tensor_table, "tensor_table", n_tensors * ctypes.sizeof(_lib.DvcAdamTensor))
+    _need_table(chunk_table, "chunk_table", n_chunks * ctypes.sizeof(_lib.DvcAdamChunk))
+    _lib.check(lib.dvc_adam_step(_p(tensor_table), n_tensors, _p(chunk_table), n_chunks, _stream()), "dvc_adam_step")

@@ -761,6 +761,44 @@ int dvc_gan_last_wgrad(const float* g, const float* x, int32_t N, int32_t Cin, i
 int dvc_gan_dot(const float* a, const float* b, int64_t count, float* out, void* workspace, size_t workspace_bytes,
                 dvcStream stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Adam: every parameter tensor of an optimiser step in ONE launch — csrc/optim.hip, driven by dvc_amd/optim.py (a drop-in for
+ * torch.optim.Adam).  The launch works from two DEVICE-resident tables the caller owns and fills: `tensors`, one DvcAdamTensor
+ * per parameter tensor, and `chunks`, which cuts every tensor into pieces of at most DVC_ADAM_CHUNK elements (chunk k of tensor
+ * i: {i, k * DVC_ADAM_CHUNK}); a workgroup walks chunks grid-stride, so a 1-element tensor and a 2.36 M-element one load the chip
+ * evenly.  Per element, all in fp32 (torch.optim.Adam's single-tensor rule):
+ *   g' = weight_decay != 0 ? fma(weight_decay, p, g) : g
+ *   m  = fma(one_minus_beta1, g' - m, m)
+ *   v  = fma(one_minus_beta2, g' * g', beta2 * v);   vmax != NULL:  vmax = max(vmax, v), and vmax takes v's place below
+ *   p  = fma(-step_size, m / fma(sqrt(v), inv_sqrt_bc2, eps), p)          (sqrt and the division correctly rounded)
+ * The scalars are per TENSOR (torch keeps `step` per parameter, and groups differ in lr): the caller evaluates them in double —
+ * step_size = lr / (1 - beta1^t), inv_sqrt_bc2 = 1 / sqrt(1 - beta2^t), 1 - beta — and rounds each once.
+ * A chunk whose p, g, m, v (and vmax) addresses are all 16-byte aligned moves as 16-byte vectors with a scalar tail; any other
+ * chunk takes the scalar path, so tensors may be views that start on any 4-byte boundary.  No element outside [0, n) of any tensor
+ * is read or written; a tensor with n == 0 needs no chunk.  Plain loads and stores, no atomics, no LDS: every element is
+ * independent, the result is bit-reproducible and does not depend on what else is in the launch.  A chunk that names a tensor
+ * outside [0, n_tensors) or a start outside [0, n) is skipped.  p, g, m, v, vmax of one tensor and of different tensors must not
+ * overlap.
+ * dvc_adam_step refuses before launching: a negative count, null tables (with tensors present), n_chunks == 0 with tensors
+ * present.  n_tensors == 0 is a successful no-op.  One launch; nothing is allocated, copied or synchronised. */
+#define DVC_ADAM_CHUNK 4096
+typedef struct DvcAdamTensor {
+    float* p;           /* parameter, updated in place */
+    const float* g;     /* gradient */
+    float* m;           /* exp_avg */
+    float* v;           /* exp_avg_sq */
+    float* vmax;        /* max_exp_avg_sq (amsgrad), or NULL */
+    int64_t n;          /* elements */
+    float step_size, inv_sqrt_bc2, beta2, one_minus_beta1, one_minus_beta2, eps, weight_decay;
+    float reserved;     /* 0 */
+} DvcAdamTensor;        /* 80 bytes */
+typedef struct DvcAdamChunk {
+    int32_t tensor;     /* index into the tensor table */
+    int32_t reserved;   /* 0 */
+    int64_t start;      /* first element of the chunk, a multiple of DVC_ADAM_CHUNK */
+} DvcAdamChunk;         /* 16 bytes */
+int dvc_adam_step(const DvcAdamTensor* tensors, int32_t n_tensors, const DvcAdamChunk* chunks, int64_t n_chunks, dvcStream stream);
+
 #ifdef DVC_DEBUG
 /* ------------------------------------------------------------------------------------------------
  * Diagnostics for the timing probes under tools/ — ONLY in a -DDVC_DEBUG build (`make -C csrc DEBUG=1` ->
