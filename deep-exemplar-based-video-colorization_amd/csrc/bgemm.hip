@@ -26,28 +26,13 @@
 // whole 16-steps, S = bg_splits(M, N, K) — a function of the sizes only, never of the batch, so an image's bits do not depend
 // on the batch around it.  Slice s of image b writes its tile to workspace[s][b][M][N]; a second launch adds the slices in
 // order s = 0 .. S-1 (and the old C last, when accumulating).  No atomics; every sum has a fixed order.  dvc_bgemm takes no
-// workspace and never splits; dvc_bgemm_splitk does when dvc_bgemm_workspace_bytes(...) > 0.
-#include "common.h"
-
-#include <algorithm>
-#include <cstdint>
+// workspace and never splits; dvc_bgemm_splitk does when dvc_bgemm_workspace_bytes(...) > 0.  The argument checks, bg_splits
+// and the slice sum live in bgemm_common.h, shared with bgemm_split3.hip.
+#include "bgemm_common.h"
 
 typedef float bg_f16v __attribute__((ext_vector_type(16)));
 
-constexpr int kBgT = 128;          // tile of C, both ways
-constexpr int kBgK = 16;           // k per step
 constexpr int kBgLd = kBgT + 4;    // LDS row stride (floats): float4 stores stay 16-byte aligned
-constexpr int kBgFill = 256;       // split until about this many workgroups per image
-constexpr int kBgMinSteps = 16;    // ... but keep at least 16 steps (256 k) per slice
-constexpr int kBgMaxSplits = 16;
-
-struct BgArgs {
-    const float* A;
-    const float* B;
-    float* C;          // the output, or the partial-sum workspace when S > 1
-    int M, N, K, S, ksteps, a_vec, b_vec, accumulate;
-    long a_sb, a_sm, a_sk, b_sb, b_sk, b_sn, c_sb, c_ss, ldc;
-};
 
 // One operand tile [16 k][128 rows] as 2 float4 per thread.  base: the image's operand; element (row, k) at row * s_row + k * s_k.
 template <bool ROW_UNIT>
@@ -171,60 +156,14 @@ __global__ __launch_bounds__(256) void bg_kernel(BgArgs a) {
     }
 }
 
-// C[b][m][n] = (C[b][m][n] +) part[0][b][m][n] + part[1][b][m][n] + ... in slice order; grid (blocks over M N, batch)
-__global__ __launch_bounds__(256) void bg_reduce_kernel(const float* __restrict__ part, float* __restrict__ C, int N, long MN, int S,
-                                                        long slice_stride, long c_sb, long ldc, int accumulate) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= MN) return;
-    const int b = blockIdx.y;
-    const float* p = part + (long)b * MN + i;
-    float s = p[0];
-    for (int k = 1; k < S; ++k) s += p[(long)k * slice_stride];
-    const long m = i / N, n = i - m * N;
-    float* dst = C + (long)b * c_sb + m * ldc + n;
-    *dst = accumulate ? *dst + s : s;
-}
-
 // ------------------------------------------------------------------------------------------------
-static int bg_splits(int M, int N, int K) {
-    const long tiles = (long)cdiv(M, kBgT) * cdiv(N, kBgT);
-    long s = kBgFill / tiles;
-    s = std::min<long>(s, cdiv(K, kBgK) / kBgMinSteps);
-    s = std::min<long>(s, kBgMaxSplits);
-    return (int)std::max<long>(s, 1);
-}
-
-static bool bg_sizes_ok(int batch, int M, int N, int K) { return batch >= 1 && M >= 1 && N >= 1 && K >= 1; }
-
-static bool bg_vec_ok(const float* p, long sb, long s_other) { return ((uintptr_t)p & 15) == 0 && sb % 4 == 0 && s_other % 4 == 0; }
-
 static int bg_run(const char* fn, const float* A, const float* B, float* C, int batch, int M, int N, int K, long a_sb, long a_sm,
                   long a_sk, long b_sb, long b_sk, long b_sn, long c_sb, long ldc, int accumulate, int S, float* workspace,
                   hipStream_t stream) {
-    DVC_REQUIRE(A && B && C, "%s: null argument", fn);
-    DVC_REQUIRE(bg_sizes_ok(batch, M, N, K), "%s: bad shape (batch %d, M %d, N %d, K %d)", fn, batch, M, N, K);
-    DVC_REQUIRE(ldc >= N, "%s: ldc (%ld) is below N (%d)", fn, ldc, N);
-    DVC_REQUIRE(a_sm == 1 || a_sk == 1, "%s: neither inner stride of A is 1 (a_sm %ld, a_sk %ld)", fn, a_sm, a_sk);
-    DVC_REQUIRE(b_sk == 1 || b_sn == 1, "%s: neither inner stride of B is 1 (b_sk %ld, b_sn %ld)", fn, b_sk, b_sn);
-    DVC_REQUIRE(a_sb >= 0 && a_sm >= 0 && a_sk >= 0 && b_sb >= 0 && b_sk >= 0 && b_sn >= 0 && c_sb >= 0,
-                "%s: negative stride", fn);
-    DVC_REQUIRE(accumulate == 0 || accumulate == 1, "%s: accumulate must be 0 or 1 (got %d)", fn, accumulate);
-    DVC_REQUIRE(cdiv(M, kBgT) <= 65535 && (long)batch * S <= 65535, "%s: M or batch too large for one launch", fn);
-    const long MN = (long)M * N;
-    DVC_REQUIRE(S == 1 || (cdivl(MN, 256) <= 0x7fffffffL && batch <= 65535), "%s: M * N too large for the split-K reduce", fn);
-
     BgArgs a;
-    a.A = A, a.B = B;
-    a.M = M, a.N = N, a.K = K, a.S = S, a.ksteps = cdiv(K, kBgK);
-    a.a_sb = a_sb, a.a_sm = a_sm, a.a_sk = a_sk, a.b_sb = b_sb, a.b_sk = b_sk, a.b_sn = b_sn;
+    if (int rc = bg_check(fn, A, B, C, batch, M, N, K, a_sb, a_sm, a_sk, b_sb, b_sk, b_sn, c_sb, ldc, accumulate, S, workspace, a))
+        return rc;
     const bool a_m_unit = a_sm == 1, b_n_unit = b_sn == 1;
-    a.a_vec = bg_vec_ok(A, a_sb, a_m_unit ? a_sk : a_sm);
-    a.b_vec = bg_vec_ok(B, b_sb, b_n_unit ? b_sk : b_sn);
-    if (S == 1) {
-        a.C = C, a.c_sb = c_sb, a.c_ss = 0, a.ldc = ldc, a.accumulate = accumulate;
-    } else {
-        a.C = workspace, a.c_sb = MN, a.c_ss = (long)batch * MN, a.ldc = N, a.accumulate = 0;
-    }
     const dim3 grid(cdiv(N, kBgT), cdiv(M, kBgT), batch * S);
     if (a_m_unit && b_n_unit)
         hipLaunchKernelGGL((bg_kernel<true, true>), grid, dim3(256), 0, stream, a);
@@ -234,17 +173,13 @@ static int bg_run(const char* fn, const float* A, const float* B, float* C, int 
         hipLaunchKernelGGL((bg_kernel<false, true>), grid, dim3(256), 0, stream, a);
     else
         hipLaunchKernelGGL((bg_kernel<false, false>), grid, dim3(256), 0, stream, a);
-    if (S > 1)
-        hipLaunchKernelGGL(bg_reduce_kernel, dim3((unsigned)cdivl(MN, 256), batch), dim3(256), 0, stream, workspace, C, N, MN, S,
-                           (long)batch * MN, c_sb, ldc, accumulate);
+    if (S > 1) bg_launch_reduce(a, C, batch, c_sb, ldc, accumulate, stream);
     DVC_CHECK_LAUNCH(fn);
     return 0;
 }
 
 extern "C" size_t dvc_bgemm_workspace_bytes(int32_t batch, int32_t M, int32_t N, int32_t K) {
-    if (!bg_sizes_ok(batch, M, N, K)) return 0;
-    const int S = bg_splits(M, N, K);
-    return S > 1 ? (size_t)S * (size_t)batch * (size_t)M * (size_t)N * sizeof(float) : 0;
+    return bg_workspace_bytes(batch, M, N, K);
 }
 
 extern "C" int dvc_bgemm(const float* A, const float* B, float* C, int32_t batch, int32_t M, int32_t N, int32_t K, int64_t a_sb,
@@ -258,16 +193,8 @@ extern "C" int dvc_bgemm_splitk(const float* A, const float* B, float* C, int32_
                                 int64_t a_sb, int64_t a_sm, int64_t a_sk, int64_t b_sb, int64_t b_sk, int64_t b_sn, int64_t c_sb,
                                 int64_t ldc, int32_t accumulate, void* workspace, size_t workspace_bytes, dvcStream stream) {
     const char* fn = "dvc_bgemm_splitk";
-    int S = 1;
-    if (bg_sizes_ok(batch, M, N, K)) {
-        S = bg_splits(M, N, K);
-        if (S > 1) {
-            const size_t need = dvc_bgemm_workspace_bytes(batch, M, N, K);
-            DVC_REQUIRE(workspace, "%s: these sizes need a workspace of %zu bytes (got NULL)", fn, need);
-            DVC_REQUIRE(workspace_bytes >= need, "%s: workspace too small (%zu bytes, need %zu)", fn, workspace_bytes, need);
-            DVC_REQUIRE(((uintptr_t)workspace & 3) == 0, "%s: workspace must be 4-byte aligned", fn);
-        }
-    }
+    int S;
+    if (int rc = bg_check_workspace(fn, batch, M, N, K, workspace, workspace_bytes, S)) return rc;
     return bg_run(fn, A, B, C, batch, M, N, K, a_sb, a_sm, a_sk, b_sb, b_sk, b_sn, c_sb, ldc, accumulate, S, (float*)workspace,
                   (hipStream_t)stream);
 }

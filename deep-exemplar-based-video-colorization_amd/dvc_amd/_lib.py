@@ -147,6 +147,9 @@ SIGNATURES = {
                                  c_i32, _VP]),
     "dvc_bgemm_splitk": (ctypes.c_int, [_VP, _VP, _VP, c_i32, c_i32, c_i32, c_i32, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64,
                                         c_i64, c_i32, _VP, ctypes.c_size_t, _VP]),
+    "dvc_bgemm_split3_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32, c_i32, c_i32]),
+    "dvc_bgemm_split3": (ctypes.c_int, [_VP, _VP, _VP, c_i32, c_i32, c_i32, c_i32, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64,
+                                        c_i64, c_i32, _VP, ctypes.c_size_t, _VP]),
     "dvc_vgg_act_bwd": (ctypes.c_int, [_VP, _VP, _VP, c_i64, _VP, _VP]),
     "dvc_vgg_pool_act_bwd": (ctypes.c_int, [_VP, _VP, _VP, _VP, c_i32, c_i32, c_i32, c_i32, _VP, _VP]),
     "dvc_vgg_conv1_bwd": (ctypes.c_int, [_VP, _VP, c_i32, c_i32, c_i32, c_i32, _VP, _VP]),

@@ -9,11 +9,13 @@ block of R rows of the "rows" operand L [B, C, Nl] against the "columns" operand
     d L_blk = M dS^T               grad_rows()
 
 `block_products(...)` picks the implementation once per autograd call: by backend() when one was selected (set_backend /
-use_backend: "vendor", "engine" or "native"), else, as ever, by ops.gemm_lib():
+use_backend: "vendor", "engine", "native" or "split3"), else, as ever, by ops.gemm_lib():
   * vendor (the default): ops.bmm on views — no staging copies, no padded last block, dS row-major only; buffers per
     (images, rows), so a ragged last block has its own;
   * native: the same views through ops.bgemm, this library's own strided fp32 MFMA GEMM (csrc/bgemm.hip) — no vendor library,
     any C; selected by name only;
+  * split3: native's loop with ops.bgemm(engine="split3") — the bf16 matrix pipes on three bf16 terms per fp32 operand
+    (csrc/bgemm_split3.hip), held to the fp32 kernel's error bound; selected by name only;
   * engine (DVC_GEMM_LIB=0): ops.conv2d with per-image filters, ksize 1, on buffers of R rows allocated once per call.  The
     block's columns of L are staged K-major (and row-major for d M) with zero rows behind a ragged block, S and dS are
     [nb, R, hm, wm] "images", the caller's kernel also writes dS^T as [nb, Nm, R/32, 32] (an image of R "pixels"), and M^T is
@@ -21,17 +23,18 @@ use_backend: "vendor", "engine" or "native"), else, as ever, by ops.gemm_lib():
 Use: images(sl_b) once per image slice; per block scores(i0, rows) first — the other three refer to that block.
 """
 import contextlib
+import functools
 
 import torch
 
 from . import ops
 
-_BACKENDS = (None, "vendor", "engine", "native")
+_BACKENDS = (None, "vendor", "engine", "native", "split3")
 _backend = None
 
 
 def backend():
-    """The selected backend: "vendor", "engine", "native", or None = ops.gemm_lib() decides between vendor and engine."""
+    """The selected backend: "vendor", "engine", "native", "split3", or None = ops.gemm_lib() decides between vendor and engine."""
     return _backend
 
 
@@ -58,7 +61,8 @@ def block_products(L, M, map_hw, R, chunk, want_rows=False, want_cols=False):
     images the caller allows per slice (`.chunk` afterwards: what the backend takes); want_rows / want_cols: whether grad_rows /
     grad_cols_accumulate will be called."""
     name = backend() or ("vendor" if ops.gemm_lib() else "engine")
-    return {"vendor": _Vendor, "engine": _Engine, "native": _Native}[name](L, M, map_hw, R, chunk, want_rows, want_cols)
+    cls = {"vendor": _Vendor, "engine": _Engine, "native": _Native, "split3": _Split3}[name]
+    return cls(L, M, map_hw, R, chunk, want_rows, want_cols)
 
 
 class _Products:
@@ -79,7 +83,7 @@ class _Products:
 
 
 class _Views(_Products):
-    """The products on views of L, M and dS; `product` is ops.bmm (_Vendor) or ops.bgemm (_Native)."""
+    """The products on views of L, M and dS; `product` is ops.bmm (_Vendor), ops.bgemm (_Native) or its split3 engine (_Split3)."""
     product = None
 
     def _alloc(self, C, Nm):
@@ -116,6 +120,10 @@ class _Vendor(_Views):
 
 class _Native(_Views):
     product = staticmethod(ops.bgemm)
+
+
+class _Split3(_Views):
+    product = staticmethod(functools.partial(ops.bgemm, engine="split3"))
 
 
 class _Engine(_Products):

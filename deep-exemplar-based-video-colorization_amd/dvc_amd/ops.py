@@ -1327,13 +1327,23 @@ def _inner_strides(t, name):
     return (0 if t.shape[0] == 1 else sb), s1, s2
 
 
-def bgemm(a, b, out=None, accumulate=False):
+_BGEMM_ENGINES = {"fp32": ("dvc_bgemm_workspace_bytes", "dvc_bgemm_splitk", "bgemm"),
+                  "split3": ("dvc_bgemm_split3_workspace_bytes", "dvc_bgemm_split3", "bgemm_split3")}
+
+
+def bgemm(a, b, out=None, accumulate=False, engine="fp32"):
     """out = a @ b (or out += a @ b) for batched fp32 matrices [B, M, K] x [B, K, N] on this library's own GEMM (dvc_bgemm_splitk,
     csrc/bgemm.hip: exact-fp32 MFMA, bit-reproducible, an image's bits independent of the batch).  Same contract as `bmm`: `a` /
     `b` may be transposed or column-sliced VIEWS, `out` a view with unit inner stride; the strides go to the kernel, nothing is
     copied.  Nothing of torch's is used, so its TF32 setting is not looked at.  Sizes with few output tiles are split over K:
     their partial sums live in the per-stream scratch cache (`_workspace`, tag "bgemm": slices x B x M x N floats, grow-only — a
-    d L = M dS^T of 16 images at R = 2048 keeps 268 MB for the life of the process)."""
+    d L = M dS^T of 16 images at R = 2048 keeps 268 MB for the life of the process).
+    engine="split3": the same contract on the bf16 matrix pipes (dvc_bgemm_split3, csrc/bgemm_split3.hip: three bf16 terms per
+    operand, eight products, fp32 accumulation; held to the fp32 kernel's error bound), with a workspace of its own (tag
+    "bgemm_split3").  Its bits differ from "fp32"'s and are as reproducible."""
+    if engine not in _BGEMM_ENGINES:
+        raise ValueError(f"dvc_amd: unknown bgemm engine {engine!r}; one of {tuple(_BGEMM_ENGINES)}")
+    ws_bytes_fn, run_fn, ws_tag = _BGEMM_ENGINES[engine]
     for t, name in ((a, "a"), (b, "b"), (out, "out")):
         if t is None:
             continue
@@ -1356,10 +1366,10 @@ def bgemm(a, b, out=None, accumulate=False):
                            f"got shape {tuple(out.shape)}, strides {tuple(out.stride())}")
     a_s, b_s = _inner_strides(a, "a"), _inner_strides(b, "b")
     lib = _lib.load()
-    nbytes = lib.dvc_bgemm_workspace_bytes(B, M, N, K)
-    ws = _workspace(a.device, nbytes, "bgemm") if nbytes else None
-    _lib.check(lib.dvc_bgemm_splitk(_p(a), _p(b), _p(out), B, M, N, K, *a_s, *b_s, 0 if B == 1 else out.stride(0), ldc,
-                                    int(bool(accumulate)), _p(ws), nbytes, _stream()), "dvc_bgemm_splitk")
+    nbytes = getattr(lib, ws_bytes_fn)(B, M, N, K)
+    ws = _workspace(a.device, nbytes, ws_tag) if nbytes else None
+    _lib.check(getattr(lib, run_fn)(_p(a), _p(b), _p(out), B, M, N, K, *a_s, *b_s, 0 if B == 1 else out.stride(0), ldc,
+                                    int(bool(accumulate)), _p(ws), nbytes, _stream()), run_fn)
     return out
 
 

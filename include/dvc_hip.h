@@ -564,6 +564,21 @@ int dvc_bgemm_splitk(const float* A, const float* B, float* C, int32_t batch, in
                      int64_t a_sm, int64_t a_sk, int64_t b_sb, int64_t b_sk, int64_t b_sn, int64_t c_sb, int64_t ldc,
                      int32_t accumulate, void* workspace, size_t workspace_bytes, dvcStream stream);
 
+/* dvc_bgemm_splitk's contract, argument for argument, on the bf16 matrix pipes — csrc/bgemm_split3.hip (opt-in: ops.bgemm's
+ * engine="split3", block_products' backend "split3").  Every fp32 operand element is split exactly into three bf16 terms
+ * (round to nearest, clamped so that no finite value rounds to infinity), eight of the nine term products run on
+ * v_mfma_f32_32x32x16_bf16 with fp32 accumulators — a1 b1 in one, the seven low-order products in another, added once at the
+ * end — and a3 b3 alone is dropped (at most 2^-32 |a||b| per product).  Same strides, tails, ldc margin,
+ * accumulate flag, refusals, split-K policy (dvc_bgemm_split3_workspace_bytes == dvc_bgemm_workspace_bytes) and
+ * reproducibility; the error bound tests hold it to is the fp32 kernel's, (K + 2) 2^-24 (|A||B| + |C0|).  Special values:
+ * zeros stay exact; a non-finite input makes the same output elements non-finite as the fp32 kernel does, though an Inf may
+ * arrive as a NaN; inputs below 2^-100 in magnitude are outside the bound (their low terms may underflow in bf16) and give
+ * finite results. */
+size_t dvc_bgemm_split3_workspace_bytes(int32_t batch, int32_t M, int32_t N, int32_t K);
+int dvc_bgemm_split3(const float* A, const float* B, float* C, int32_t batch, int32_t M, int32_t N, int32_t K, int64_t a_sb,
+                     int64_t a_sm, int64_t a_sk, int64_t b_sb, int64_t b_sk, int64_t b_sn, int64_t c_sb, int64_t ldc,
+                     int32_t accumulate, void* workspace, size_t workspace_bytes, dvcStream stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Input gradient of VGG19_pytorch (frozen weights) and of tensor_lab2rgb — csrc/vgg_bwd.hip.  The 3x3 convolutions' input
  * gradients run on dvc_conv2d / dvc_conv2d_winograd / dvc_conv2d_ws with the transposed, flipped filters; these are the steps

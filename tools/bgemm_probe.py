@@ -1,12 +1,14 @@
-"""The training side's three row-block products on the three backends of dvc_amd.block_products — "native" (csrc/bgemm.hip through
-ops.bgemm), "vendor" (torch.bmm) and "engine" (the 1x1-convolution engine) — at the production shape of the fused correlation's
+"""The training side's three row-block products on the four backends of dvc_amd.block_products — "split3" (csrc/bgemm_split3.hip:
+three bf16 terms per operand on the bf16 MFMA), "native" (csrc/bgemm.hip through ops.bgemm), "vendor" (torch.bmm) and "engine"
+(the 1x1-convolution engine) — at the production shape of the fused correlation's
 backward: C = 256, P = 54 x 96 = 5184 positions, row blocks of R = 2048, one image and the 16 images that BLOCK_BYTES allows per
 slice at batch 16.  Each product is issued alone, exactly as block_products issues it (the engine's staging copies and the
 staged copy of a partial grad_rows included), then the whole backward passes of fused_correlation and ContextualLoss.
 
 GPU time by HIP events with the launch queue primed (tools/probe_timing.py); the backends alternate inside every round, all in
-one process; median and p10..p90 over the rounds.  TFLOP/s = 2 nb R P C / median; the share is of the 157.3 TFLOP/s fp32 matrix
-peak of the MI355X.  The table goes to stdout and to --out (default profiles/bgemm_probe.txt).
+one process; median and p10..p90 over the rounds.  TFLOP/s = 2 nb R P C / median (the fp32 product's operations, whatever
+the backend spends on them); the share is of the 157.3 TFLOP/s fp32 matrix peak of the MI355X, and for split3 of an eighth of the
+2500 TFLOP/s dense bf16 peak (eight bf16 products per fp32 product: 312.5 TFLOP/s).  The table goes to stdout and to --out (default profiles/bgemm_probe.txt).
 
     python tools/bgemm_probe.py [--out FILE] [--rounds N] [--trace]
 
@@ -26,7 +28,8 @@ from dvc_amd import block_products as bp, contextual, corr_autograd, ops  # noqa
 from probe_timing import device_time, spread  # noqa: E402
 
 PEAK = 157.3
-BACKENDS = ("native", "vendor", "engine")
+PEAKS = {"split3": 2500.0 / 8}                    # the others: PEAK
+BACKENDS = ("split3", "native", "vendor", "engine")
 C, H, W, R = 256, 54, 96, 2048
 P = H * W
 
@@ -93,7 +96,8 @@ def main():
         torch.cuda.synchronize()
         return
     lines = [f"torch {torch.__version__}; {torch.cuda.get_device_name(0)}; C={C} P={H}x{W}={P} R={R}; {args.rounds} rounds, "
-             f"backends alternating; ms = median (p10..p90); TF = TFLOP/s at the median; share of {PEAK} TFLOP/s fp32 matrix peak"]
+             f"backends alternating; ms = median (p10..p90); TF = TFLOP/s at the median; share of {PEAK} TFLOP/s fp32 matrix peak "
+             f"(split3: of {PEAKS['split3']:.1f} = the dense bf16 peak / 8)"]
 
     def run(title, per_backend, flops, reps):
         """per_backend: {backend: callable}; one line per backend."""
@@ -109,10 +113,11 @@ def main():
         for n, s in samples.items():
             lo, m, hi = spread(s)
             med[n] = m
-            rate = f"  {flops / m / 1e9:6.1f} TF  {100 * flops / m / 1e9 / PEAK:5.1f} %" if flops else ""
+            rate = f"  {flops / m / 1e9:6.1f} TF  {100 * flops / m / 1e9 / PEAKS.get(n, PEAK):5.1f} %" if flops else ""
             lines.append(f"    {n:7s} {m:9.3f} ms ({lo:.3f}..{hi:.3f}){rate}")
         lines.append("    native / vendor = %.2f, native / engine = %.2f" % (med["native"] / med["vendor"], med["native"] / med["engine"]))
-        print("\n".join(lines[-(len(per_backend) + 2):]), flush=True)
+        lines.append("    split3 / native = %.2f, split3 / vendor = %.2f" % (med["split3"] / med["native"], med["split3"] / med["vendor"]))
+        print("\n".join(lines[-(len(per_backend) + 3):]), flush=True)
 
     print(lines[0], flush=True)
     for nb in (1, 16):
