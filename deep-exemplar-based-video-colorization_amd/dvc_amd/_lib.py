@@ -60,6 +60,18 @@ class DvcAdamChunk(ctypes.Structure):
     _fields_ = [("tensor", c_i32), ("reserved", c_i32), ("start", c_i64)]
 
 
+class DvcLossTerm(ctypes.Structure):
+    _fields_ = [
+        ("x", ctypes.c_void_p), ("t", ctypes.c_void_p), ("w", ctypes.c_void_p), ("dx", ctypes.c_void_p), ("dt", ctypes.c_void_p),
+        ("n", c_i64), ("plane", c_i64), ("cpl", c_i64), ("p", c_i32), ("reserved", c_i32),
+        ("t_scalar", ctypes.c_float), ("scale", ctypes.c_float),
+    ]
+
+
+class DvcLossChunk(ctypes.Structure):
+    _fields_ = [("term", c_i32), ("reserved", c_i32), ("start", c_i64)]
+
+
 # every symbol include/dvc_hip.h declares: name -> (restype, argtypes)
 _VP = ctypes.c_void_p
 SIGNATURES = {
@@ -193,6 +205,8 @@ SIGNATURES = {
     "dvc_gan_last_wgrad": (ctypes.c_int, [_VP, _VP, c_i32, c_i32, c_i32, c_i32, c_i64, _VP, _VP]),
     "dvc_gan_dot": (ctypes.c_int, [_VP, _VP, c_i64, _VP, _VP, ctypes.c_size_t, _VP]),
     "dvc_adam_step": (ctypes.c_int, [_VP, c_i32, _VP, c_i64, _VP]),
+    "dvc_loss_fwd": (ctypes.c_int, [_VP, _VP, c_i32, _VP, c_i64, _VP, _VP, _VP]),
+    "dvc_loss_bwd": (ctypes.c_int, [_VP, _VP, c_i32, _VP, c_i64, _VP, _VP, _VP]),
 }
 # diagnostics for tools/ (include/dvc_hip.h, last section): exported by the -DDVC_DEBUG build only
 DEBUG_SIGNATURES = {

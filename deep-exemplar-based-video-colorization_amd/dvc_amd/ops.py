@@ -1867,3 +1867,43 @@ def adam_step(tensor_table, n_tensors, chunk_table, n_chunks):
     _need_table(tensor_table, "tensor_table", n_tensors * ctypes.sizeof(_lib.DvcAdamTensor))
     _need_table(chunk_table, "chunk_table", n_chunks * ctypes.sizeof(_lib.DvcAdamChunk))
     _lib.check(lib.dvc_adam_step(_p(tensor_table), n_tensors, _p(chunk_table), n_chunks, _stream()), "dvc_adam_step")
+
+
+# ---- the pixel losses (csrc/loss.hip; dvc_amd/losses.py fills the tables)
+def _need_host_table(t, name, nbytes):
+    if not isinstance(t, torch.Tensor) or t.device.type != "cpu":
+        raise RuntimeError(f"dvc_amd: `{name}` must be the host copy of the table (a CPU uint8 tensor)")
+    if t.dtype != torch.uint8 or not t.is_contiguous() or t.numel() < nbytes or t.data_ptr() % 8:
+        raise RuntimeError(f"dvc_amd: `{name}` must be a contiguous 8-byte aligned uint8 tensor of at least {nbytes} bytes")
+
+
+def loss_fwd(term_table, term_table_host, n_terms, chunk_table, n_chunks, partials, values):
+    """dvc_loss_fwd: two launches that reduce every term of the device-resident tables — uint8 device tensors that hold n_terms
+    DvcLossTerm and n_chunks DvcLossChunk records (dvc_amd.losses.build_tables lays them out; `term_table_host` is the host copy
+    the library validates) — into `partials` (float64, n_chunks) and `values` (float32, n_terms + 1: the terms, then the total)."""
+    lib = _lib.load()
+    _need_table(term_table, "term_table", n_terms * ctypes.sizeof(_lib.DvcLossTerm))
+    _need_host_table(term_table_host, "term_table_host", n_terms * ctypes.sizeof(_lib.DvcLossTerm))
+    _need_table(chunk_table, "chunk_table", n_chunks * ctypes.sizeof(_lib.DvcLossChunk))
+    if not partials.is_cuda or partials.dtype != torch.float64 or not partials.is_contiguous() or partials.numel() < n_chunks:
+        raise RuntimeError(f"dvc_amd: `partials` must be a contiguous float64 device tensor of at least {n_chunks} elements")
+    _need(values, "values")
+    if values.numel() < n_terms + 1:
+        raise RuntimeError(f"dvc_amd: `values` must hold {n_terms + 1} floats")
+    _lib.check(lib.dvc_loss_fwd(_p(term_table), _p(term_table_host), n_terms, _p(chunk_table), n_chunks, _p(partials), _p(values),
+                                _stream()), "dvc_loss_fwd")
+
+
+def loss_bwd(term_table, term_table_host, n_terms, chunk_table, n_chunks, grad_total, grad_values=None):
+    """dvc_loss_bwd: ONE launch that writes dx / dt of every term of the tables (as for loss_fwd, with the gradient addresses
+    filled in) from the device scalars `grad_total` (1 float) and `grad_values` (n_terms floats, or None for zeros)."""
+    lib = _lib.load()
+    _need_table(term_table, "term_table", n_terms * ctypes.sizeof(_lib.DvcLossTerm))
+    _need_host_table(term_table_host, "term_table_host", n_terms * ctypes.sizeof(_lib.DvcLossTerm))
+    _need_table(chunk_table, "chunk_table", n_chunks * ctypes.sizeof(_lib.DvcLossChunk))
+    _need(grad_total, "grad_total")
+    _need(grad_values, "grad_values")
+    if grad_total.numel() < 1 or (grad_values is not None and grad_values.numel() < n_terms):
+        raise RuntimeError(f"dvc_amd: `grad_total` must hold 1 float and `grad_values` {n_terms}")
+    _lib.check(lib.dvc_loss_bwd(_p(term_table), _p(term_table_host), n_terms, _p(chunk_table), n_chunks, _p(grad_total),
+                                _p(grad_values), _stream()), "dvc_loss_bwd")

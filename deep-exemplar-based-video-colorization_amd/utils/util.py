@@ -5,7 +5,9 @@ test.py:20-21 does
                             save_frames, tensor_lab2rgb, uncenter_l)
 The tensor helpers on the hot path (`tensor_lab2rgb`, `uncenter_l`, `gray2rgb_batch`,
 `feature_normalize`, `vgg_preprocess`, `center_l`, `center_ab`) are this package's HIP-backed
-versions (dvc_amd/util.py).  Every other name (`save_frames`, `folder2vid`, `mkdir_if_not`,
+versions (dvc_amd/util.py), and so are the four pixel losses train.py imports (`mse_loss`, `l1_loss`,
+`weighted_mse_loss`, `weighted_l1_loss`: dvc_amd/losses.py, one fused HIP reduction forward and one
+launch backward).  Every other name (`save_frames`, `folder2vid`, `mkdir_if_not`,
 `batch_lab2rgb_transpose_mc`, the plotting / training helpers ...) is forwarded, on first use, to the
 next `utils/util.py` found on `utils.__path__` — i.e. the reference's own file, loaded unmodified
 under the module name `utils._reference_util`.  Its import errors (cv2 / skimage / torchvision
@@ -17,6 +19,7 @@ import sys as _sys
 
 from dvc_amd.util import (ab_mean, ab_norm, center_ab, center_l, feature_normalize,  # noqa: F401
                           gray2rgb_batch, l_mean, l_norm, tensor_lab2rgb, uncenter_l, vgg_preprocess)
+from dvc_amd.losses import l1_loss, mse_loss, weighted_l1_loss, weighted_mse_loss  # noqa: F401
 
 _HERE = _os.path.dirname(_os.path.abspath(__file__))
 _REF_NAME = "utils._reference_util"

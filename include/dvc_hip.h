@@ -814,6 +814,55 @@ typedef struct DvcAdamChunk {
 } DvcAdamChunk;         /* 16 bytes */
 int dvc_adam_step(const DvcAdamTensor* tensors, int32_t n_tensors, const DvcAdamChunk* chunks, int64_t n_chunks, dvcStream stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Pixel losses: every term scale * mean_i(w * |x_i - t_i|^p), p in {1, 2}, of a training step on one fused reduction —
+ * csrc/loss.hip, driven by dvc_amd/losses.py (train.py's mse_loss / l1_loss / weighted_mse_loss / weighted_l1_loss).  As for Adam,
+ * the launches work from two DEVICE-resident tables the caller owns: `terms`, one DvcLossTerm per term, and `chunks`, which cuts
+ * every term into pieces of at most DVC_LOSS_CHUNK elements, terms in order, chunk j of term k at start j * DVC_LOSS_CHUNK.
+ * `terms_host` is the caller's HOST copy of the term table (the staging buffer the device copy was sent from): every refusal below
+ * is decided from it before anything is launched, and the kernels never see it.
+ *   x: n contiguous floats.  t: n floats, or NULL for the scalar t_scalar.  w: NULL; n floats (cpl == 0); or a [B,1,H,W] mask
+ *   broadcast over the channels of x [B,C,H,W] (plane = H*W, cpl = C*plane): element i reads w[(i / cpl) * plane + i % plane].
+ * Per element, in fp32 and with no contraction: d = x - t, e = d*d or |d|, v = w*e (v = e without w; a NaN under a zero weight
+ * stays a NaN).  Chunks whose x, t (dx, dt) addresses are 16-byte aligned move as 16-byte vectors, any other chunk element by
+ * element; a full-shape w likewise from its own address, a broadcast w as vectors only when also plane % 4 == 0.
+ * dvc_loss_fwd, two launches.  Stage 1: thread j of the 256 of a chunk adds the v of elements 4 (j + 256 r) + k (r = 0..3, k = 0..3)
+ *   into a double, in that order whichever path loaded them; the 256 doubles are combined by block_sum (csrc/reduce.h: butterfly in
+ *   the wave, the four waves in CHAIN order) and stored to partials[chunk] — a function of the chunk's data alone.  Stage 2, one
+ *   workgroup: per term, thread j adds the term's partials j, j + 256, ..., block_sum gives S_k;
+ *   values[k] = (float)(S_k * (double)scale_k / n_k), and values[n_terms] = (float) of those doubles added in term order.
+ *   A term's value is therefore bit-identical alone and inside any table.  No atomics; nothing is allocated or synchronised.
+ * dvc_loss_bwd, one launch: c_k = (float)(((double)grad_total[0] + grad_values[k]) * scale_k / n_k) from device memory (grad_values
+ *   may be NULL: zeros); dx_i = (2 c_k * w_i) * d_i for p = 2, (c_k * w_i) * sgn(d_i) for p = 1 with sgn(0) = 0; dt_i = -dx_i; each
+ *   is stored only where its pointer is non-NULL, and a term with neither is not touched.  Forward ignores dx and dt.
+ * Both refuse before launching: a negative count; null tables, n_chunks == 0, or n_chunks != sum ceil(n_k / DVC_LOSS_CHUNK) with
+ * terms present; p outside {1, 2}; n <= 0; null x; plane <= 0, cpl % plane != 0 or n % cpl != 0; null partials / values /
+ * grad_total.  n_terms == 0 is a successful no-op.  A chunk that names a term outside [0, n_terms) or a start outside [0, n) is
+ * skipped (its partial is 0).  dx and dt must not overlap x, t, w or each other. */
+#define DVC_LOSS_CHUNK 4096
+typedef struct DvcLossTerm {
+    const float* x;     /* input */
+    const float* t;     /* target of x's shape, or NULL: t_scalar */
+    const float* w;     /* weights (see cpl), or NULL */
+    float* dx;          /* backward: gradient to x, or NULL */
+    float* dt;          /* backward: gradient to t, or NULL */
+    int64_t n;          /* elements of x */
+    int64_t plane;      /* H*W of a broadcast w; 1 otherwise */
+    int64_t cpl;        /* C*H*W of a broadcast w; 0: w has x's shape */
+    int32_t p;          /* 1: |d|, 2: d*d */
+    int32_t reserved;   /* 0 */
+    float t_scalar, scale;
+} DvcLossTerm;          /* 80 bytes */
+typedef struct DvcLossChunk {
+    int32_t term;       /* index into the term table */
+    int32_t reserved;   /* 0 */
+    int64_t start;      /* first element of the chunk, a multiple of DVC_LOSS_CHUNK */
+} DvcLossChunk;         /* 16 bytes */
+int dvc_loss_fwd(const DvcLossTerm* terms, const DvcLossTerm* terms_host, int32_t n_terms, const DvcLossChunk* chunks,
+                 int64_t n_chunks, double* partials, float* values, dvcStream stream);
+int dvc_loss_bwd(const DvcLossTerm* terms, const DvcLossTerm* terms_host, int32_t n_terms, const DvcLossChunk* chunks,
+                 int64_t n_chunks, const float* grad_total, const float* grad_values, dvcStream stream);
+
 #ifdef DVC_DEBUG
 /* ------------------------------------------------------------------------------------------------
  * Diagnostics for the timing probes under tools/ — ONLY in a -DDVC_DEBUG build (`make -C csrc DEBUG=1` ->
