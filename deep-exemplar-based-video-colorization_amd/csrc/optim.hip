@@ -8,6 +8,9 @@
 //
 // The arithmetic is spelled with explicit fmaf and the file is compiled with contraction off, so the roundings are the ones
 // written here whatever the compiler's default: tests/adam_reference.py counts them.
+//
+// dvc_adam_advance (below the step kernel) is the capturable variant's second launch: it keeps the step counts and the two
+// bias-correction columns of the tensor table on the device, so that dvc_adam_step, unchanged, can be replayed from a graph.
 #include "common.h"
 
 #include <cstdint>
@@ -15,6 +18,7 @@
 #pragma clang fp contract(off)
 
 static_assert(sizeof(DvcAdamTensor) == 80 && sizeof(DvcAdamChunk) == 16, "table layouts are part of the ABI (dvc_amd/_lib.py)");
+static_assert(sizeof(DvcAdamAdvance) == 40, "table layouts are part of the ABI (dvc_amd/_lib.py)");
 
 namespace {
 
@@ -114,7 +118,37 @@ __global__ __launch_bounds__(kAdamBlock) void adam_step_kernel(const DvcAdamTens
     }
 }
 
+// The device-side half of a capturable step: one thread per tensor advances that tensor's step count and rewrites the two
+// columns of its record that depend on it, in double as optim.adam_scalars does on the host.  Everything else in the record is
+// the caller's.  A few dozen threads of work; what it buys is that nothing per step comes from the host.
+constexpr int kAdvanceBlock = 64;
+
+__global__ __launch_bounds__(kAdvanceBlock) void adam_advance_kernel(const DvcAdamAdvance* __restrict__ advance,
+                                                                     DvcAdamTensor* __restrict__ tensors, int n_tensors) {
+    const int i = blockIdx.x * kAdvanceBlock + threadIdx.x;
+    if (i >= n_tensors) return;
+    const DvcAdamAdvance a = advance[i];
+    const float t = *a.step + 1.0f;
+    *a.step = t;
+    const double lr = a.lr_tensor ? (double)*a.lr_tensor : a.lr;
+    const double bc1 = 1.0 - pow(a.beta1, (double)t);
+    const double bc2 = 1.0 - pow(a.beta2, (double)t);
+    tensors[i].step_size = (float)(lr / bc1);
+    tensors[i].inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+}
+
 }  // namespace
+
+extern "C" int dvc_adam_advance(const DvcAdamAdvance* advance, DvcAdamTensor* tensors, int32_t n_tensors, dvcStream stream) {
+    const char* fn = "dvc_adam_advance";
+    DVC_REQUIRE(n_tensors >= 0, "%s: negative count (%d tensors)", fn, n_tensors);
+    if (n_tensors == 0) return 0;
+    DVC_REQUIRE(advance && tensors, "%s: null table", fn);
+    hipLaunchKernelGGL(adam_advance_kernel, dim3((unsigned)cdiv(n_tensors, kAdvanceBlock)), dim3(kAdvanceBlock), 0,
+                       (hipStream_t)stream, advance, tensors, (int)n_tensors);
+    DVC_CHECK_LAUNCH(fn);
+    return 0;
+}
 
 extern "C" int dvc_adam_step(const DvcAdamTensor* tensors, int32_t n_tensors, const DvcAdamChunk* chunks, int64_t n_chunks,
                              dvcStream stream) {

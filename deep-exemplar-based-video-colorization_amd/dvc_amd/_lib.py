@@ -60,6 +60,11 @@ class DvcAdamChunk(ctypes.Structure):
     _fields_ = [("tensor", c_i32), ("reserved", c_i32), ("start", c_i64)]
 
 
+class DvcAdamAdvance(ctypes.Structure):
+    _fields_ = [("step", ctypes.c_void_p), ("lr_tensor", ctypes.c_void_p), ("lr", ctypes.c_double), ("beta1", ctypes.c_double),
+                ("beta2", ctypes.c_double)]
+
+
 class DvcLossTerm(ctypes.Structure):
     _fields_ = [
         ("x", ctypes.c_void_p), ("t", ctypes.c_void_p), ("w", ctypes.c_void_p), ("dx", ctypes.c_void_p), ("dt", ctypes.c_void_p),
@@ -205,6 +210,7 @@ SIGNATURES = {
     "dvc_gan_last_wgrad": (ctypes.c_int, [_VP, _VP, c_i32, c_i32, c_i32, c_i32, c_i64, _VP, _VP]),
     "dvc_gan_dot": (ctypes.c_int, [_VP, _VP, c_i64, _VP, _VP, ctypes.c_size_t, _VP]),
     "dvc_adam_step": (ctypes.c_int, [_VP, c_i32, _VP, c_i64, _VP]),
+    "dvc_adam_advance": (ctypes.c_int, [_VP, _VP, c_i32, _VP]),
     "dvc_loss_fwd": (ctypes.c_int, [_VP, _VP, c_i32, _VP, c_i64, _VP, _VP, _VP]),
     "dvc_loss_bwd": (ctypes.c_int, [_VP, _VP, c_i32, _VP, c_i64, _VP, _VP, _VP]),
 }

@@ -1869,6 +1869,16 @@ def adam_step(tensor_table, n_tensors, chunk_table, n_chunks):
     _lib.check(lib.dvc_adam_step(_p(tensor_table), n_tensors, _p(chunk_table), n_chunks, _stream()), "dvc_adam_step")
 
 
+def adam_advance(advance_table, tensor_table, n_tensors):
+    """dvc_adam_advance: ONE launch that advances every tensor's device-resident step count and rewrites the step_size and
+    inv_sqrt_bc2 columns of `tensor_table` from it — uint8 device tensors that hold n_tensors DvcAdamAdvance and DvcAdamTensor
+    records (dvc_amd.optim.CapturableAdam lays them out).  dvc_adam_step follows on the same table and stream."""
+    lib = _lib.load()
+    _need_table(advance_table, "advance_table", n_tensors * ctypes.sizeof(_lib.DvcAdamAdvance))
+    _need_table(tensor_table, "tensor_table", n_tensors * ctypes.sizeof(_lib.DvcAdamTensor))
+    _lib.check(lib.dvc_adam_advance(_p(advance_table), _p(tensor_table), n_tensors, _stream()), "dvc_adam_advance")
+
+
 # ---- the pixel losses (csrc/loss.hip; dvc_amd/losses.py fills the tables)
 def _need_host_table(t, name, nbytes):
     if not isinstance(t, torch.Tensor) or t.device.type != "cpu":

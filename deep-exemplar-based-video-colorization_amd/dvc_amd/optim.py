@@ -11,6 +11,10 @@ Per step the host evaluates each tensor's scalars in double (per TENSOR: torch k
 stream and launches once.  Two staging buffers alternate, each behind an event recorded after its copy, so a step never
 overwrites a buffer whose copy has not run yet.  The scalars change every step, so a step cannot be replayed from a captured
 graph: `step()` raises while the current stream is capturing.
+
+`CapturableAdam` (below) is the variant that can: torch's `capturable=True` contract.  Its `step` tensors live on the device, a
+second small launch (dvc_adam_advance) advances them and rewrites the two step-dependent columns of the tensor table there, and the
+tables stay resident between steps, so a step whose addresses did not move is two launches and nothing else — eagerly or replayed.
 """
 import math
 
@@ -23,6 +27,7 @@ from . import _lib, ops
 CHUNK = 4096  # elements per chunk == DVC_ADAM_CHUNK of include/dvc_hip.h (tests/test_adam_host.py holds the two together)
 TENSOR_DTYPE = np.dtype(_lib.DvcAdamTensor)
 CHUNK_DTYPE = np.dtype(_lib.DvcAdamChunk)
+ADVANCE_DTYPE = np.dtype(_lib.DvcAdamAdvance)      # (CapturableAdam's third table)
 _REFUSED_FLAGS = ("maximize", "capturable", "differentiable", "decoupled_weight_decay")
 
 
@@ -78,15 +83,20 @@ class Adam(Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, *, foreach=None,
                  maximize=False, capturable=False, differentiable=False, fused=None, decoupled_weight_decay=False):
         if isinstance(lr, torch.Tensor):
-            raise NotImplementedError("dvc_amd.optim.Adam: a tensor `lr` is not supported (the step's scalars are evaluated on "
-                                      "the host); pass a float")
+            if not self._capturable:
+                raise NotImplementedError("dvc_amd.optim.Adam: a tensor `lr` is not supported (the step's scalars are evaluated on "
+                                          "the host); pass a float, or use dvc_amd.optim.CapturableAdam")
+            if lr.numel() != 1 or lr.dtype != torch.float32:
+                raise ValueError(f"{self._name}: a tensor `lr` must be a one-element float32 tensor")
         if any(isinstance(b, torch.Tensor) for b in betas):
-            raise NotImplementedError("dvc_amd.optim.Adam: tensor `betas` are not supported; pass floats")
-        for name, value in (("maximize", maximize), ("capturable", capturable), ("differentiable", differentiable),
-                            ("decoupled_weight_decay", decoupled_weight_decay), ("foreach", foreach), ("fused", fused)):
+            raise NotImplementedError(f"{self._name}: tensor `betas` are not supported; pass floats")
+        for name, value in (("maximize", maximize), ("capturable", capturable and not self._capturable),
+                            ("differentiable", differentiable), ("decoupled_weight_decay", decoupled_weight_decay),
+                            ("foreach", foreach), ("fused", fused)):
             if value:
-                raise NotImplementedError(f"dvc_amd.optim.Adam: `{name}=True` is not supported by the HIP step")
-        if not 0.0 <= lr:
+                raise NotImplementedError(f"{self._name}: `{name}=True` is not supported by the HIP step"
+                                          + ("; use dvc_amd.optim.CapturableAdam" if name == "capturable" else ""))
+        if not isinstance(lr, torch.Tensor) and not 0.0 <= lr:         # (a tensor lr lives on the device and is never read back)
             raise ValueError(f"Invalid learning rate: {lr}")
         if not 0.0 <= eps:
             raise ValueError(f"Invalid epsilon value: {eps}")
@@ -98,7 +108,7 @@ class Adam(Optimizer):
             raise ValueError(f"Invalid weight_decay value: {weight_decay}")
         # the keys torch.optim.Adam keeps in a group, so that either class loads the other's state_dict
         defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=False,
-                        foreach=None, capturable=False, differentiable=False, fused=None, decoupled_weight_decay=False)
+                        foreach=None, capturable=self._capturable, differentiable=False, fused=None, decoupled_weight_decay=False)
         super().__init__(params, defaults)
 
     def __setstate__(self, state):
@@ -114,16 +124,27 @@ class Adam(Optimizer):
                 if len(st) and not torch.is_tensor(st["step"]):
                     st["step"] = torch.tensor(float(st["step"]), dtype=torch.float32)
 
+    # ---- what CapturableAdam answers differently
+    _name = "dvc_amd.optim.Adam"
+    _capturable = False
+    _refused_flags = _REFUSED_FLAGS
+
+    def _check_group(self, group):
+        if isinstance(group["lr"], torch.Tensor) or any(isinstance(b, torch.Tensor) for b in group["betas"]):
+            raise NotImplementedError(f"{self._name}: a tensor `lr` / `betas` is not supported; pass floats")
+
+    def _new_step(self, p):
+        return torch.tensor(0.0, dtype=torch.float32)
+
     # ---- one step
     def _collect(self):
         """Validate everything and create missing state; nothing is advanced.  -> [(group, p, grad, state)]"""
         work = []
         for group in self.param_groups:
-            for name in _REFUSED_FLAGS:
+            for name in self._refused_flags:
                 if group.get(name):
-                    raise NotImplementedError(f"dvc_amd.optim.Adam: `{name}=True` is not supported by the HIP step")
-            if isinstance(group["lr"], torch.Tensor) or any(isinstance(b, torch.Tensor) for b in group["betas"]):
-                raise NotImplementedError("dvc_amd.optim.Adam: a tensor `lr` / `betas` is not supported; pass floats")
+                    raise NotImplementedError(f"{self._name}: `{name}=True` is not supported by the HIP step")
+            self._check_group(group)
             for p in group["params"]:
                 grad = p.grad
                 if grad is None:
@@ -131,39 +152,39 @@ class Adam(Optimizer):
                 if grad.is_sparse:
                     raise RuntimeError("Adam does not support sparse gradients, please consider SparseAdam instead")
                 if not p.is_cuda or not grad.is_cuda:
-                    raise RuntimeError("dvc_amd.optim.Adam: parameters and gradients must be ROCm device tensors; the HIP step has "
+                    raise RuntimeError(f"{self._name}: parameters and gradients must be ROCm device tensors; the HIP step has "
                                        "no CPU fallback")
                 if p.dtype != torch.float32 or grad.dtype != torch.float32:
-                    raise TypeError(f"dvc_amd.optim.Adam: parameters and gradients must be float32 (got {p.dtype}, {grad.dtype})")
+                    raise TypeError(f"{self._name}: parameters and gradients must be float32 (got {p.dtype}, {grad.dtype})")
                 if not p.is_contiguous():
-                    raise ValueError(f"dvc_amd.optim.Adam: a parameter of shape {tuple(p.shape)} and strides {p.stride()} is not "
+                    raise ValueError(f"{self._name}: a parameter of shape {tuple(p.shape)} and strides {p.stride()} is not "
                                      "contiguous")
                 if grad.shape != p.shape:
-                    raise ValueError(f"dvc_amd.optim.Adam: gradient shape {tuple(grad.shape)} != parameter {tuple(p.shape)}")
+                    raise ValueError(f"{self._name}: gradient shape {tuple(grad.shape)} != parameter {tuple(p.shape)}")
                 state = self.state[p]
                 if len(state) == 0:
-                    state["step"] = torch.tensor(0.0, dtype=torch.float32)
+                    state["step"] = self._new_step(p)
                     state["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                     state["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                     if group["amsgrad"]:
                         state["max_exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                 elif group["amsgrad"] and "max_exp_avg_sq" not in state:
-                    raise RuntimeError("dvc_amd.optim.Adam: amsgrad was switched on for a parameter whose state has no max_exp_avg_sq")
+                    raise RuntimeError(f"{self._name}: amsgrad was switched on for a parameter whose state has no max_exp_avg_sq")
                 for key in ("exp_avg", "exp_avg_sq") + (("max_exp_avg_sq",) if group["amsgrad"] else ()):
                     s = state[key]
                     if not s.is_cuda:
-                        raise RuntimeError(f"dvc_amd.optim.Adam: state `{key}` is a CPU tensor; the HIP step has no CPU fallback")
+                        raise RuntimeError(f"{self._name}: state `{key}` is a CPU tensor; the HIP step has no CPU fallback")
                     if s.dtype != torch.float32:
-                        raise TypeError(f"dvc_amd.optim.Adam: state `{key}` must be float32 (got {s.dtype})")
+                        raise TypeError(f"{self._name}: state `{key}` must be float32 (got {s.dtype})")
                     if not s.is_contiguous() or s.numel() != p.numel():
-                        raise ValueError(f"dvc_amd.optim.Adam: state `{key}` must be contiguous with {p.numel()} elements")
+                        raise ValueError(f"{self._name}: state `{key}` must be contiguous with {p.numel()} elements")
                 work.append((group, p, grad, state))
         if work:
             dev = ops._current_device()
             for _, p, grad, state in work:
                 for t in (p, grad, state["exp_avg"], state["exp_avg_sq"], state.get("max_exp_avg_sq")):
                     if t is not None and t.device.index != dev:
-                        raise RuntimeError(f"dvc_amd.optim.Adam: a tensor lives on {t.device} but the current device is cuda:{dev}; "
+                        raise RuntimeError(f"{self._name}: a tensor lives on {t.device} but the current device is cuda:{dev}; "
                                            "call torch.cuda.set_device / use torch.cuda.device(...)")
         return work
 
@@ -171,7 +192,8 @@ class Adam(Optimizer):
     def step(self, closure=None):
         if torch.cuda.is_initialized() and torch.cuda.is_current_stream_capturing():       # before anything is allocated or launched
             raise RuntimeError("dvc_amd.optim.Adam: step() cannot be captured into a graph: its scalars (the bias corrections of "
-                               "step t) change every step and are launch-time table entries; step outside the capture")
+                               "step t) change every step and are launch-time table entries; step outside the capture, or use "
+                               "dvc_amd.optim.CapturableAdam")
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -228,3 +250,240 @@ class Adam(Optimizer):
             st.event[slot] = torch.cuda.Event()
         st.event[slot].record()
         ops.adam_step(table, n_t, table[t_bytes:], n_c)
+
+
+# ---- the capturable variant: step counts and bias terms kept on the device
+def fingerprint(work):
+    """What a set of resident tables was built from, for `work` = [(group, p, grad, state)] (gradients contiguous): per group with
+    work its lr (a tensor lr by address), betas, eps, weight_decay and amsgrad; per tensor its group, the five addresses (vmax 0
+    without amsgrad), n and the address of its `step`.  Equal fingerprints <=> the tables a rebuild would write are the ones
+    already on the device; a parameter whose gradient went to None drops out of `work` and so changes it."""
+    groups, index, tensors = [], {}, []
+    for group, p, grad, state in work:
+        gi = index.get(id(group))
+        if gi is None:
+            gi = index[id(group)] = len(groups)
+            lr = group["lr"]
+            groups.append((("tensor", lr.data_ptr()) if isinstance(lr, torch.Tensor) else lr, group["betas"][0], group["betas"][1],
+                           group["eps"], group["weight_decay"], bool(group["amsgrad"])))
+        tensors.append((gi, p.data_ptr(), grad.data_ptr(), state["exp_avg"].data_ptr(), state["exp_avg_sq"].data_ptr(),
+                        state["max_exp_avg_sq"].data_ptr() if group["amsgrad"] else 0, p.numel(), state["step"].data_ptr()))
+    return groups, tensors
+
+
+def build_capturable_tables(work):
+    """The three tables of a capturable step from `work` = [(group, p, grad, state)]: (TENSOR_DTYPE, CHUNK_DTYPE, ADVANCE_DTYPE)
+    arrays, one tensor and one advance record per entry.  step_size and inv_sqrt_bc2 are left 0: dvc_adam_advance writes them on
+    the device before every dvc_adam_step; the other five scalar columns are adam_scalars' (they do not depend on the step)."""
+    tensors = np.zeros(len(work), dtype=TENSOR_DTYPE)
+    advance = np.zeros(len(work), dtype=ADVANCE_DTYPE)
+    for i, (group, p, grad, state) in enumerate(work):
+        beta1, beta2 = group["betas"]
+        lr = group["lr"]
+        vmax = state["max_exp_avg_sq"].data_ptr() if group["amsgrad"] else 0
+        sc = adam_scalars(1, 0.0, beta1, beta2, group["eps"], group["weight_decay"])
+        tensors[i] = (p.data_ptr(), grad.data_ptr(), state["exp_avg"].data_ptr(), state["exp_avg_sq"].data_ptr(), vmax, p.numel(),
+                      0.0, 0.0) + sc[2:]
+        if isinstance(lr, torch.Tensor):
+            advance[i] = (state["step"].data_ptr(), lr.data_ptr(), 0.0, beta1, beta2)
+        else:
+            advance[i] = (state["step"].data_ptr(), 0, lr, beta1, beta2)
+    return tensors, chunk_table([w[1].numel() for w in work]), advance
+
+
+class _Resident:
+    """One table tensor on the device ([tensor records | chunk records | advance records]) and what it was built from."""
+
+    def __init__(self, key, table, n_t, n_c, params, pinned, stream):
+        t_bytes, c_bytes = n_t * TENSOR_DTYPE.itemsize, n_c * CHUNK_DTYPE.itemsize       # (80 n_t + 16 n_c: every table 8-byte aligned)
+        self.key, self.table, self.n_t, self.n_c, self.params = key, table, n_t, n_c, params
+        self.chunks, self.advance = table[t_bytes:t_bytes + c_bytes], table[t_bytes + c_bytes:]
+        self.pinned = pinned        # the buffer a CAPTURED upload reads on every replay (None for an eager upload)
+        self.stream = stream        # the last stream it was used on
+        self.captured = False
+
+
+class CapturableAdam(Adam):
+    """torch.optim.Adam(capturable=True) on two HIP launches per step: dvc_adam_advance, then the unchanged dvc_adam_step.
+
+    The constructor is `Adam`'s, except that `lr` may also be a one-element fp32 device tensor and `capturable` is True.
+    `state["step"]` is a device fp32 scalar per parameter, and `state_dict()` / `load_state_dict()` are interchangeable with
+    `torch.optim.Adam(capturable=True)` in both directions; a CPU `step` loaded from a plain Adam is moved to the device once, and
+    nothing ever reads a `step` back.
+
+    The tensor, chunk and advance tables live in ONE device tensor the optimiser owns.  A step validates as `Adam` does (a refused
+    step advances nothing), fingerprints the addresses, element counts and hyper-parameters (`fingerprint`), and if nothing moved
+    since the tables were uploaded it is exactly two launches: no copy, no allocation, no host arithmetic.  If something moved
+    (a reallocated `.grad`, a gradient that went to None, a scheduler's new float `lr`, a loaded state) the tables are rebuilt and
+    uploaded from a pinned buffer under `_Staging`'s discipline.
+
+    `step()` works under `torch.cuda.graph`.  Take one eager step (or load a state_dict) first: state created during a capture
+    would be zeroed again by every replay, so a captured step refuses to create it.  Tables uploaded during a capture are sent
+    from a pinned buffer of their own that is never rewritten, so the replay's copy node re-sends the same bytes, and the advance
+    launch that follows rewrites the two step-dependent columns from the device `step`: a replay is correct whatever the copy
+    restored.  Tables a graph refers to stay alive as long as the optimiser.  A float `lr` changed by a scheduler is seen by the
+    next eager `step()` but not by a replay (it is baked into the captured tables); a tensor `lr` updated in place is seen by
+    both.
+
+    A replay runs no host code, so it cannot bump the parameters' version counters as the eager `step()` does: call
+    `mark_updated()` after every replay.  Without it the modules' packed-weight caches, which are keyed on the version, go stale,
+    and a graph that saved a parameter does not refuse its backward."""
+
+    _name = "dvc_amd.optim.CapturableAdam"
+    _capturable = True
+    _refused_flags = tuple(f for f in _REFUSED_FLAGS if f != "capturable")
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, *, foreach=None,
+                 maximize=False, capturable=True, differentiable=False, fused=None, decoupled_weight_decay=False):
+        if not capturable:
+            raise ValueError("dvc_amd.optim.CapturableAdam: `capturable=False` is dvc_amd.optim.Adam")
+        super().__init__(params, lr, betas, eps, weight_decay, amsgrad, foreach=foreach, maximize=maximize, capturable=True,
+                         differentiable=differentiable, fused=fused, decoupled_weight_decay=decoupled_weight_decay)
+        self._ensure_spare()
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        for group in self.param_groups:
+            group["capturable"] = True
+            for p in group["params"]:
+                st = self.state.get(p)
+                if st:
+                    st["step"] = self._device_step(st["step"], p)
+
+    def add_param_group(self, param_group):
+        super().add_param_group(param_group)
+        if "_dvc_spare" in self.__dict__:       # (not while the constructor is still adding its groups)
+            self._ensure_spare()
+
+    @staticmethod
+    def _device_step(step, p):
+        """`step` as a float32 tensor on p's device (a CPU step of a plain Adam's state_dict is moved once, never read)."""
+        if step.device != p.device or step.dtype != torch.float32:
+            step = step.detach().to(device=p.device, dtype=torch.float32)
+        return step
+
+    def _check_group(self, group):
+        if any(isinstance(b, torch.Tensor) for b in group["betas"]):
+            raise NotImplementedError(f"{self._name}: tensor `betas` are not supported; pass floats")
+        lr = group["lr"]
+        if isinstance(lr, torch.Tensor):
+            if lr.numel() != 1 or lr.dtype != torch.float32:
+                raise ValueError(f"{self._name}: a tensor `lr` must be a one-element float32 tensor")
+            if not lr.is_cuda:
+                raise RuntimeError(f"{self._name}: a tensor `lr` must be a ROCm device tensor; the HIP step has no CPU fallback")
+
+    def _new_step(self, p):
+        return torch.zeros((), dtype=torch.float32, device=p.device)
+
+    def _collect(self):
+        work = super()._collect()
+        for _, p, _, state in work:
+            step = state["step"]
+            if not torch.is_tensor(step) or step.numel() != 1:
+                raise ValueError(f"{self._name}: state `step` must be a one-element tensor")
+            if step.device != p.device or step.dtype != torch.float32:
+                state["step"] = self._device_step(step, p)
+        return work
+
+    # ---- pinned memory for an upload that is itself captured
+    def _table_bytes_bound(self):
+        params = [p for group in self.param_groups for p in group["params"]]
+        n_c = sum((p.numel() + CHUNK - 1) // CHUNK for p in params)
+        return len(params) * (TENSOR_DTYPE.itemsize + ADVANCE_DTYPE.itemsize) + n_c * CHUNK_DTYPE.itemsize
+
+    def _ensure_spare(self):
+        """Keep one pinned buffer, large enough for the tables of every parameter, allocated OUTSIDE any capture: pinned memory
+        cannot be relied on to be allocatable while a stream is capturing, and a captured upload needs a buffer of its own."""
+        need = self._table_bytes_bound()
+        spare = self.__dict__.setdefault("_dvc_spare", None)
+        if spare is not None and spare.numel() >= need:
+            return
+        if need == 0 or not any(p.is_cuda for group in self.param_groups for p in group["params"]):
+            return
+        if torch.cuda.is_current_stream_capturing():
+            return
+        self.__dict__["_dvc_spare"] = torch.empty(need, dtype=torch.uint8, pin_memory=True)
+
+    # ---- one step
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        capturing = torch.cuda.is_initialized() and torch.cuda.is_current_stream_capturing()
+        if capturing:
+            for group in self.param_groups:
+                for p in group["params"]:
+                    if p.grad is not None and len(self.state.get(p, ())) == 0:
+                        raise RuntimeError(f"{self._name}: a parameter has no state yet and the stream is capturing: every replay "
+                                           "would zero it again; take one eager step() or load a state_dict before the capture")
+        work = self._collect()
+        if not work:
+            return loss
+        if not all(w[2].is_contiguous() for w in work):
+            work = [(g, p, grad if grad.is_contiguous() else grad.contiguous(), st) for g, p, grad, st in work]
+        key = fingerprint(work)
+        res = self.__dict__.get("_dvc_resident")
+        if res is None or res.key != key:
+            res = self._upload(work, key, capturing)
+        stream = ops._stream_handle()
+        if capturing:
+            if not res.captured:        # a graph refers to these tables from now on: they live as long as the optimiser
+                res.captured = True
+                self.__dict__.setdefault("_dvc_captured", []).append(res)
+        elif stream != res.stream:
+            if not res.captured:        # (allocated on another stream: the allocator must not reuse it under this one's launches)
+                res.table.record_stream(torch.cuda.current_stream())
+            res.stream = stream
+        ops.adam_advance(res.advance, res.table, res.n_t)
+        if res.n_c:
+            ops.adam_step(res.table, res.n_t, res.chunks, res.n_c)
+        # the kernel wrote the parameters behind autograd's back: a graph that saved one must refuse its backward
+        torch.autograd.graph.increment_version(res.params)
+        if not capturing and self.__dict__.get("_dvc_spare") is None:
+            self._ensure_spare()
+        return loss
+
+    def mark_updated(self):
+        """Bump the version counter of every parameter the resident tables update — what the eager `step()` does after its
+        launches, and what a graph replay cannot do: host-only, no GPU work.  Call it after every replay of a captured step."""
+        res = self.__dict__.get("_dvc_resident")
+        if res is not None:
+            torch.autograd.graph.increment_version(res.params)
+
+    def _upload(self, work, key, capturing):
+        """Rebuild the three tables and send them to a fresh table tensor with one host-to-device copy on the current stream."""
+        tensors, chunks, advance = build_capturable_tables(work)
+        n_t, n_c = len(tensors), len(chunks)
+        t_bytes, c_bytes, a_bytes = tensors.nbytes, chunks.nbytes, advance.nbytes
+        nbytes = t_bytes + c_bytes + a_bytes
+        st = None
+        if capturing:       # a buffer of its own, never rewritten: the replay's copy node reads it again
+            pinned = self.__dict__.get("_dvc_spare")
+            self.__dict__["_dvc_spare"] = None
+            if pinned is None or pinned.numel() < nbytes:
+                pinned = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+        else:
+            st = self.__dict__.get("_dvc_staging")
+            if st is None:
+                st = self.__dict__["_dvc_staging"] = _Staging()
+            slot = st.slot = 1 - st.slot
+            if st.event[slot] is not None:
+                st.event[slot].synchronize()        # the copy that last read this buffer (two uploads ago) has run
+            if st.buf[slot] is None or st.buf[slot].numel() < nbytes:
+                st.buf[slot] = torch.empty(nbytes + nbytes // 4, dtype=torch.uint8, pin_memory=True)
+            pinned = st.buf[slot]
+        host = pinned.numpy()
+        host[:t_bytes].view(TENSOR_DTYPE)[:] = tensors
+        host[t_bytes:t_bytes + c_bytes].view(CHUNK_DTYPE)[:] = chunks
+        host[t_bytes + c_bytes:nbytes].view(ADVANCE_DTYPE)[:] = advance
+        table = torch.empty(nbytes, dtype=torch.uint8, device=work[0][1].device)
+        table.copy_(pinned[:nbytes], non_blocking=True)
+        if st is not None:
+            if st.event[slot] is None:
+                st.event[slot] = torch.cuda.Event()
+            st.event[slot].record()
+        res = _Resident(key, table, n_t, n_c, [w[1] for w in work], pinned if capturing else None, ops._stream_handle())
+        self.__dict__["_dvc_resident"] = res
+        return res

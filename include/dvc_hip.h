@@ -814,6 +814,23 @@ typedef struct DvcAdamChunk {
 } DvcAdamChunk;         /* 16 bytes */
 int dvc_adam_step(const DvcAdamTensor* tensors, int32_t n_tensors, const DvcAdamChunk* chunks, int64_t n_chunks, dvcStream stream);
 
+/* The step count and the two bias-correction columns kept on the DEVICE (dvc_amd.optim.CapturableAdam, torch's capturable=True
+ * contract): one launch, ahead of dvc_adam_step on the same stream and the same tensor table, in which one thread per tensor does
+ *   t = *step + 1;  *step = t;                      lr_i = lr_tensor ? *lr_tensor : lr
+ *   tensors[i].step_size    = (float)(lr_i / (1 - pow(beta1, t)))          (double throughout, rounded once)
+ *   tensors[i].inv_sqrt_bc2 = (float)(1 / sqrt(1 - pow(beta2, t)))
+ * and touches nothing else of the record: the addresses, n and the other five scalar columns stay as the caller wrote them.  The
+ * step therefore depends on nothing the host computes per step, and the pair of launches can be replayed from a captured graph.
+ * `step` (and `lr_tensor`, when not NULL) are one-element fp32 device tensors; the `step` of different records must not alias.
+ * dvc_adam_advance refuses before launching: a negative count, null tables (with tensors present).  n_tensors == 0 is a
+ * successful no-op.  One launch; nothing is allocated, copied or synchronised. */
+typedef struct DvcAdamAdvance {
+    float* step;                /* the tensor's step count, advanced in place */
+    const float* lr_tensor;     /* NULL: use `lr` */
+    double lr, beta1, beta2;
+} DvcAdamAdvance;       /* 40 bytes */
+int dvc_adam_advance(const DvcAdamAdvance* advance, DvcAdamTensor* tensors, int32_t n_tensors, dvcStream stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Pixel losses: every term scale * mean_i(w * |x_i - t_i|^p), p in {1, 2}, of a training step on one fused reduction —
  * csrc/loss.hip, driven by dvc_amd/losses.py (train.py's mse_loss / l1_loss / weighted_mse_loss / weighted_l1_loss).  As for Adam,

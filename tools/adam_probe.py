@@ -1,5 +1,6 @@
-"""What one optimiser step costs on the real parameter sets: dvc_amd.optim.Adam (one dvc_adam_step launch) beside torch.optim.Adam in
-its default mode, with foreach=True and with fused=True.  Per set: GPU time of the kernel alone (HIP events, launch queue primed,
+"""What one optimiser step costs on the real parameter sets: dvc_amd.optim.Adam (one dvc_adam_step launch) and
+dvc_amd.optim.CapturableAdam (dvc_adam_advance + dvc_adam_step on resident tables: eager with unchanged gradient addresses, and as a
+replayed one-step graph followed by mark_updated()) beside torch.optim.Adam in its default mode, with foreach=True and with fused=True.  Per set: GPU time of the kernel alone (HIP events, launch queue primed,
 launches on a resident table), GPU-side time of back-to-back step() calls (events; this is max(host, GPU) when the host is the
 slower side), host time to issue a step (host clock around step() calls that end in one synchronise, queue drained first), and the
 kernel's achieved bytes/s against the 28 B / element Adam has to move, as a fraction of the chip's measured HBM rate.
@@ -76,7 +77,7 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "adam_probe.txt"))
     args = ap.parse_args()
     assert torch.cuda.is_available(), "adam_probe needs a GPU"
-    from dvc_amd.optim import Adam
+    from dvc_amd.optim import Adam, CapturableAdam
     lines = [f"Adam step on the real parameter sets, lr {LR}, betas {BETAS}, {torch.cuda.get_device_name(0)}; ms as p10 / median / p90 of "
              f"{ROUNDS} rounds x {REPS} steps"]
     for name, groups in parameter_sets():
@@ -88,6 +89,7 @@ def main():
         lines.append(f"{name}: {len(params)} tensors, {n:,} elements ({min(p.numel() for p in params):,} .. {max(p.numel() for p in params):,}), "
                      f"{28 * n / 1e6:.1f} MB to move per step")
         makers = [("dvc_amd.optim.Adam", lambda gs: Adam(gs, lr=LR, betas=BETAS)),
+                  ("CapturableAdam, eager", lambda gs: CapturableAdam(gs, lr=LR, betas=BETAS)),
                   ("torch default", lambda gs: torch.optim.Adam(gs, lr=LR, betas=BETAS)),
                   ("torch foreach=True", lambda gs: torch.optim.Adam(gs, lr=LR, betas=BETAS, foreach=True)),
                   ("torch fused=True", lambda gs: torch.optim.Adam(gs, lr=LR, betas=BETAS, fused=True))]
@@ -110,7 +112,27 @@ def main():
                              f"8.0 TB/s data sheet (resident p, g, m, v: {16 * n / 2**20:.0f} MiB against the 256 MiB Infinity Cache, "
                              f"which back-to-back launches on one table can hit)")
                 medians["kernel"] = k[1]
+            if label == "CapturableAdam, eager":           # the same optimiser, one step captured (gradient addresses unchanged)
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph):
+                    opt.step()
+
+                def replay():
+                    graph.replay()
+                    opt.mark_updated()
+
+                replay()
+                torch.cuda.synchronize()
+                gpu = T.spread([T.device_time(replay, REPS, warm=False) for _ in range(ROUNDS)])
+                host = host_issue_ms(replay)
+                medians["CapturableAdam, replay"] = (gpu[1], host[1])
+                lines.append(f"  {'CapturableAdam replay':<20s} replay + mark_updated, GPU side {gpu[0]:.3f} / {gpu[1]:.3f} / {gpu[2]:.3f} ms   host issue "
+                             f"{host[0]:.3f} / {host[1]:.3f} / {host[2]:.3f} ms")
         ours, fused, default = medians["dvc_amd.optim.Adam"], medians["torch fused=True"], medians["torch default"]
+        eager, replayed = medians["CapturableAdam, eager"], medians["CapturableAdam, replay"]
+        lines.append(f"  host issue, CapturableAdam / Adam: eager {eager[1] / ours[1]:.2f}, replay {replayed[1] / ours[1]:.2f}   "
+                     f"CapturableAdam / torch fused: eager {eager[1] / fused[1]:.2f}, replay {replayed[1] / fused[1]:.2f}   "
+                     f"GPU side, CapturableAdam / torch fused: eager {eager[0] / fused[0]:.2f}, replay {replayed[0] / fused[0]:.2f}")
         lines.append(f"  GPU side, dvc / torch fused: {ours[0] / fused[0]:.2f}   host issue, dvc / torch default: {ours[1] / default[1]:.2f}   "
                      f"kernel alone / torch fused GPU side: {medians['kernel'] / fused[0]:.2f}")
     text = "\n".join(lines) + "\n"
