@@ -65,6 +65,11 @@ class DvcAdamAdvance(ctypes.Structure):
                 ("beta2", ctypes.c_double)]
 
 
+class DvcGradGuard(ctypes.Structure):
+    _fields_ = [("total_norm", ctypes.c_float), ("clip_coef", ctypes.c_float), ("found_inf", c_i32), ("skipped", c_i32),
+                ("sumsq", ctypes.c_double)]
+
+
 class DvcLossTerm(ctypes.Structure):
     _fields_ = [
         ("x", ctypes.c_void_p), ("t", ctypes.c_void_p), ("w", ctypes.c_void_p), ("dx", ctypes.c_void_p), ("dt", ctypes.c_void_p),
@@ -211,6 +216,10 @@ SIGNATURES = {
     "dvc_gan_dot": (ctypes.c_int, [_VP, _VP, c_i64, _VP, _VP, ctypes.c_size_t, _VP]),
     "dvc_adam_step": (ctypes.c_int, [_VP, c_i32, _VP, c_i64, _VP]),
     "dvc_adam_advance": (ctypes.c_int, [_VP, _VP, c_i32, _VP]),
+    "dvc_grad_norm": (ctypes.c_int, [_VP, c_i32, _VP, c_i64, _VP, ctypes.c_double, ctypes.c_uint32, _VP, _VP]),
+    "dvc_adam_advance_guarded": (ctypes.c_int, [_VP, _VP, c_i32, _VP, _VP]),
+    "dvc_adam_step_guarded": (ctypes.c_int, [_VP, c_i32, _VP, c_i64, _VP, _VP]),
+    "dvc_grad_scale": (ctypes.c_int, [_VP, c_i32, _VP, c_i64, _VP, _VP]),
     "dvc_loss_fwd": (ctypes.c_int, [_VP, _VP, c_i32, _VP, c_i64, _VP, _VP, _VP]),
     "dvc_loss_bwd": (ctypes.c_int, [_VP, _VP, c_i32, _VP, c_i64, _VP, _VP, _VP]),
 }

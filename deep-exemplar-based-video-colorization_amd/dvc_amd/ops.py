@@ -1879,6 +1879,59 @@ def adam_advance(advance_table, tensor_table, n_tensors):
     _lib.check(lib.dvc_adam_advance(_p(advance_table), _p(tensor_table), n_tensors, _stream()), "dvc_adam_advance")
 
 
+# ---- the gradient guard (csrc/optim.hip; dvc_amd.optim.GuardedAdam / grad_norm / clip_grad_norm_ own the record)
+GRAD_NORM_KEEP_NONFINITE = 1        # == DVC_GRAD_NORM_KEEP_NONFINITE of include/dvc_hip.h
+
+
+def _need_guard(guard):
+    _need_table(guard, "guard", ctypes.sizeof(_lib.DvcGradGuard))
+
+
+def grad_norm(tensor_table, n_tensors, chunk_table, n_chunks, partials, max_norm, guard, keep_nonfinite=False):
+    """dvc_grad_norm: two launches that reduce sum g^2 over every tensor of the two tables (those of adam_step) into `partials`
+    (float64, n_chunks) and write the DvcGradGuard record `guard` (a 24-byte uint8 device tensor): norm, clip_grad_norm_'s
+    coefficient for `max_norm` (float("inf"): none), the non-finite flag (left 0 with keep_nonfinite) and the skip count."""
+    lib = _lib.load()
+    _need_table(tensor_table, "tensor_table", n_tensors * ctypes.sizeof(_lib.DvcAdamTensor))
+    _need_table(chunk_table, "chunk_table", n_chunks * ctypes.sizeof(_lib.DvcAdamChunk))
+    if not isinstance(partials, torch.Tensor) or not partials.is_cuda:
+        raise RuntimeError("dvc_amd: `partials` must be a ROCm device tensor; the HIP path has no CPU fallback")
+    if partials.dtype != torch.float64 or not partials.is_contiguous() or partials.numel() < n_chunks:
+        raise RuntimeError(f"dvc_amd: `partials` must be a contiguous float64 device tensor of at least {n_chunks} elements")
+    _need_guard(guard)
+    _lib.check(lib.dvc_grad_norm(_p(tensor_table), n_tensors, _p(chunk_table), n_chunks, _p(partials), float(max_norm),
+                                 GRAD_NORM_KEEP_NONFINITE if keep_nonfinite else 0, _p(guard), _stream()), "dvc_grad_norm")
+
+
+def adam_advance_guarded(advance_table, tensor_table, n_tensors, guard):
+    """dvc_adam_advance_guarded: adam_advance, unless `guard` has its non-finite flag set — then nothing is touched."""
+    lib = _lib.load()
+    _need_table(advance_table, "advance_table", n_tensors * ctypes.sizeof(_lib.DvcAdamAdvance))
+    _need_table(tensor_table, "tensor_table", n_tensors * ctypes.sizeof(_lib.DvcAdamTensor))
+    _need_guard(guard)
+    _lib.check(lib.dvc_adam_advance_guarded(_p(advance_table), _p(tensor_table), n_tensors, _p(guard), _stream()),
+               "dvc_adam_advance_guarded")
+
+
+def adam_step_guarded(tensor_table, n_tensors, chunk_table, n_chunks, guard):
+    """dvc_adam_step_guarded: adam_step on clip_coef * g, or nothing at all when `guard` has its non-finite flag set."""
+    lib = _lib.load()
+    _need_table(tensor_table, "tensor_table", n_tensors * ctypes.sizeof(_lib.DvcAdamTensor))
+    _need_table(chunk_table, "chunk_table", n_chunks * ctypes.sizeof(_lib.DvcAdamChunk))
+    _need_guard(guard)
+    _lib.check(lib.dvc_adam_step_guarded(_p(tensor_table), n_tensors, _p(chunk_table), n_chunks, _p(guard), _stream()),
+               "dvc_adam_step_guarded")
+
+
+def grad_scale(tensor_table, n_tensors, chunk_table, n_chunks, guard):
+    """dvc_grad_scale: ONE launch that multiplies every gradient of the tables by the coefficient in `guard`, in place."""
+    lib = _lib.load()
+    _need_table(tensor_table, "tensor_table", n_tensors * ctypes.sizeof(_lib.DvcAdamTensor))
+    _need_table(chunk_table, "chunk_table", n_chunks * ctypes.sizeof(_lib.DvcAdamChunk))
+    _need_guard(guard)
+    _lib.check(lib.dvc_grad_scale(_p(tensor_table), n_tensors, _p(chunk_table), n_chunks, _p(guard), _stream()), "dvc_grad_scale")
+
+
 # ---- the pixel losses (csrc/loss.hip; dvc_amd/losses.py fills the tables)
 def _need_host_table(t, name, nbytes):
     if not isinstance(t, torch.Tensor) or t.device.type != "cpu":

@@ -15,6 +15,11 @@ graph: `step()` raises while the current stream is capturing.
 `CapturableAdam` (below) is the variant that can: torch's `capturable=True` contract.  Its `step` tensors live on the device, a
 second small launch (dvc_adam_advance) advances them and rewrites the two step-dependent columns of the tensor table there, and the
 tables stay resident between steps, so a step whose addresses did not move is two launches and nothing else — eagerly or replayed.
+
+`GuardedAdam` (at the bottom) is `CapturableAdam` with a look at its gradients first: dvc_grad_norm reduces their global L2 norm
+into a small device record, and the guarded advance and step obey it — clip_grad_norm_'s coefficient goes into the step as one
+multiply of g, and a NaN or Inf anywhere skips the whole step, count and all.  Four launches, no host code between them.
+`grad_norm` and `clip_grad_norm_` are the same reduction as stand-alone functions (torch.nn.utils.clip_grad_norm_'s signature).
 """
 import math
 
@@ -28,6 +33,7 @@ CHUNK = 4096  # elements per chunk == DVC_ADAM_CHUNK of include/dvc_hip.h (tests
 TENSOR_DTYPE = np.dtype(_lib.DvcAdamTensor)
 CHUNK_DTYPE = np.dtype(_lib.DvcAdamChunk)
 ADVANCE_DTYPE = np.dtype(_lib.DvcAdamAdvance)      # (CapturableAdam's third table)
+GUARD_DTYPE = np.dtype(_lib.DvcGradGuard)          # (GuardedAdam's device record)
 _REFUSED_FLAGS = ("maximize", "capturable", "differentiable", "decoupled_weight_decay")
 
 
@@ -81,7 +87,11 @@ class Adam(Optimizer):
     """torch.optim.Adam on one HIP launch per step.  See the module docstring."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, *, foreach=None,
-                 maximize=False, capturable=False, differentiable=False, fused=None, decoupled_weight_decay=False):
+                 maximize=False, capturable=False, differentiable=False, fused=None, decoupled_weight_decay=False,
+                 max_grad_norm=None, skip_nonfinite=None):
+        if not self._guarded and (max_grad_norm is not None or skip_nonfinite is not None):
+            raise NotImplementedError(f"{self._name}: `max_grad_norm` / `skip_nonfinite` are not supported by this step; use "
+                                      "dvc_amd.optim.GuardedAdam")
         if isinstance(lr, torch.Tensor):
             if not self._capturable:
                 raise NotImplementedError("dvc_amd.optim.Adam: a tensor `lr` is not supported (the step's scalars are evaluated on "
@@ -127,6 +137,7 @@ class Adam(Optimizer):
     # ---- what CapturableAdam answers differently
     _name = "dvc_amd.optim.Adam"
     _capturable = False
+    _guarded = False
     _refused_flags = _REFUSED_FLAGS
 
     def _check_group(self, group):
@@ -297,7 +308,10 @@ class _Resident:
     def __init__(self, key, table, n_t, n_c, params, pinned, stream):
         t_bytes, c_bytes = n_t * TENSOR_DTYPE.itemsize, n_c * CHUNK_DTYPE.itemsize       # (80 n_t + 16 n_c: every table 8-byte aligned)
         self.key, self.table, self.n_t, self.n_c, self.params = key, table, n_t, n_c, params
-        self.chunks, self.advance = table[t_bytes:t_bytes + c_bytes], table[t_bytes + c_bytes:]
+        a_end = t_bytes + c_bytes + n_t * ADVANCE_DTYPE.itemsize
+        self.chunks, self.advance = table[t_bytes:t_bytes + c_bytes], table[t_bytes + c_bytes:a_end]
+        self.scratch = table[a_end:]        # (CapturableAdam._scratch_bytes: empty unless a subclass asks for some)
+        self.guard = None                   # (GuardedAdam: the record its launches on these tables write, kept alive with them)
         self.pinned = pinned        # the buffer a CAPTURED upload reads on every replay (None for an eager upload)
         self.stream = stream        # the last stream it was used on
         self.captured = False
@@ -334,11 +348,13 @@ class CapturableAdam(Adam):
     _refused_flags = tuple(f for f in _REFUSED_FLAGS if f != "capturable")
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, *, foreach=None,
-                 maximize=False, capturable=True, differentiable=False, fused=None, decoupled_weight_decay=False):
+                 maximize=False, capturable=True, differentiable=False, fused=None, decoupled_weight_decay=False,
+                 max_grad_norm=None, skip_nonfinite=None):
         if not capturable:
-            raise ValueError("dvc_amd.optim.CapturableAdam: `capturable=False` is dvc_amd.optim.Adam")
+            raise ValueError(f"{self._name}: `capturable=False` is dvc_amd.optim.Adam")
         super().__init__(params, lr, betas, eps, weight_decay, amsgrad, foreach=foreach, maximize=maximize, capturable=True,
-                         differentiable=differentiable, fused=fused, decoupled_weight_decay=decoupled_weight_decay)
+                         differentiable=differentiable, fused=fused, decoupled_weight_decay=decoupled_weight_decay,
+                         max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
         self._ensure_spare()
 
     def __setstate__(self, state):
@@ -436,14 +452,22 @@ class CapturableAdam(Adam):
             if not res.captured:        # (allocated on another stream: the allocator must not reuse it under this one's launches)
                 res.table.record_stream(torch.cuda.current_stream())
             res.stream = stream
-        ops.adam_advance(res.advance, res.table, res.n_t)
-        if res.n_c:
-            ops.adam_step(res.table, res.n_t, res.chunks, res.n_c)
+        self._launch_resident(res, capturing)
         # the kernel wrote the parameters behind autograd's back: a graph that saved one must refuse its backward
         torch.autograd.graph.increment_version(res.params)
         if not capturing and self.__dict__.get("_dvc_spare") is None:
             self._ensure_spare()
         return loss
+
+    def _launch_resident(self, res, capturing):
+        """The launches of one step on resident tables (GuardedAdam puts the norm in front and uses the guarded pair)."""
+        ops.adam_advance(res.advance, res.table, res.n_t)
+        if res.n_c:
+            ops.adam_step(res.table, res.n_t, res.chunks, res.n_c)
+
+    def _scratch_bytes(self, n_c):
+        """Bytes of device scratch kept behind the three tables, in the same tensor (GuardedAdam: the norm's partials)."""
+        return 0
 
     def mark_updated(self):
         """Bump the version counter of every parameter the resident tables update — what the eager `step()` does after its
@@ -478,8 +502,8 @@ class CapturableAdam(Adam):
         host[:t_bytes].view(TENSOR_DTYPE)[:] = tensors
         host[t_bytes:t_bytes + c_bytes].view(CHUNK_DTYPE)[:] = chunks
         host[t_bytes + c_bytes:nbytes].view(ADVANCE_DTYPE)[:] = advance
-        table = torch.empty(nbytes, dtype=torch.uint8, device=work[0][1].device)
-        table.copy_(pinned[:nbytes], non_blocking=True)
+        table = torch.empty(nbytes + self._scratch_bytes(n_c), dtype=torch.uint8, device=work[0][1].device)
+        table[:nbytes].copy_(pinned[:nbytes], non_blocking=True)
         if st is not None:
             if st.event[slot] is None:
                 st.event[slot] = torch.cuda.Event()
@@ -487,3 +511,225 @@ class CapturableAdam(Adam):
         res = _Resident(key, table, n_t, n_c, [w[1] for w in work], pinned if capturing else None, ops._stream_handle())
         self.__dict__["_dvc_resident"] = res
         return res
+
+
+# ---- the gradient guard: norm, clipping, non-finite skip
+_NONFINITE_MESSAGE = ("The total norm of order {} for gradients from `parameters` is non-finite, so it cannot be clipped. To disable "
+                      "this error and scale the gradients by the non-finite norm anyway, set `error_if_nonfinite=False`")
+
+
+def _checked_max_norm(max_norm, where):
+    """`max_norm` as a float; None is +inf (no clipping).  NaN and values <= 0 are refused, as dvc_grad_norm refuses them."""
+    if max_norm is None:
+        return math.inf
+    if isinstance(max_norm, torch.Tensor):
+        raise NotImplementedError(f"{where}: a tensor `max_norm` is not supported (it is a launch argument); pass a float")
+    max_norm = float(max_norm)
+    if not max_norm > 0.0:
+        raise ValueError(f"{where}: `max_norm` must be a positive number or None (got {max_norm})")
+    return max_norm
+
+
+def new_guard(device):
+    """A zeroed DvcGradGuard record on `device`, as the uint8 tensor the launch wrappers take."""
+    return torch.zeros(GUARD_DTYPE.itemsize, dtype=torch.uint8, device=device)
+
+
+def guard_views(guard):
+    """(total_norm, skipped) of a guard record as 0-dim device tensors that VIEW it: float32 and int32."""
+    return guard[0:4].view(torch.float32)[0], guard[12:16].view(torch.int32)[0]
+
+
+def read_guard(guard):
+    """The record read back as a dict of Python numbers (total_norm, clip_coef, found_inf, skipped, sumsq).  Synchronises."""
+    rec = guard.cpu().numpy().view(GUARD_DTYPE)[0]
+    return {name: rec[name].item() for name in GUARD_DTYPE.names}
+
+
+def build_norm_tables(grads):
+    """The two tables dvc_grad_norm / dvc_grad_scale walk for the contiguous fp32 tensors `grads`, through build_tables: only g and n
+    of a record are filled in, the four other addresses and the scalars are 0 (those kernels read nothing else)."""
+    zeros = (0.0,) * 8
+    return build_tables([(0, g.data_ptr(), 0, 0, 0, g.numel(), zeros) for g in grads])
+
+
+_functional_staging = _Staging()
+
+
+def _gradients(parameters, where, in_place):
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    grads = [p.grad for p in parameters if p.grad is not None]
+    for g in grads:
+        if g.is_sparse:
+            raise NotImplementedError(f"{where}: sparse gradients are not supported")
+        if not g.is_cuda:
+            raise RuntimeError(f"{where}: gradients must be ROCm device tensors; the HIP reduction has no CPU fallback")
+        if g.dtype != torch.float32:
+            raise TypeError(f"{where}: gradients must be float32 (got {g.dtype})")
+        if in_place and not g.is_contiguous():
+            raise ValueError(f"{where}: a gradient of shape {tuple(g.shape)} and strides {g.stride()} is not contiguous and cannot "
+                             "be scaled in place")
+    if grads:
+        dev = ops._current_device()
+        for g in grads:
+            if g.device.index != dev:
+                raise RuntimeError(f"{where}: a gradient lives on {g.device} but the current device is cuda:{dev}; call "
+                                   "torch.cuda.set_device / use torch.cuda.device(...)")
+    return [g if g.is_contiguous() else g.contiguous() for g in grads]
+
+
+def _functional_norm(grads, max_norm, where):
+    """Upload the tables of `grads` under _Staging's discipline and launch dvc_grad_norm.  -> (table, n_t, chunks, n_c, guard)"""
+    if torch.cuda.is_initialized() and torch.cuda.is_current_stream_capturing():        # before anything is allocated or launched
+        raise RuntimeError(f"{where} cannot be captured into a graph: its tables carry the gradients' addresses and are launch-time "
+                           "data; call it outside the capture, or use dvc_amd.optim.GuardedAdam")
+    tensors, chunks = build_norm_tables(grads)
+    n_t, n_c = len(tensors), len(chunks)
+    t_bytes, nbytes = tensors.nbytes, tensors.nbytes + chunks.nbytes
+    st = _functional_staging
+    slot = st.slot = 1 - st.slot
+    if st.event[slot] is not None:
+        st.event[slot].synchronize()        # the copy that last read this buffer (two calls ago) has run
+    if st.buf[slot] is None or st.buf[slot].numel() < nbytes:
+        st.buf[slot] = torch.empty(nbytes + nbytes // 4, dtype=torch.uint8, pin_memory=True)
+    host = st.buf[slot].numpy()
+    host[:t_bytes].view(TENSOR_DTYPE)[:] = tensors
+    host[t_bytes:nbytes].view(CHUNK_DTYPE)[:] = chunks
+    device = grads[0].device
+    table = torch.empty(nbytes + 8 * n_c, dtype=torch.uint8, device=device)     # (tables | partials; freed on return, in stream order)
+    table[:nbytes].copy_(st.buf[slot][:nbytes], non_blocking=True)
+    st.event[slot] = torch.cuda.Event()
+    st.event[slot].record()
+    guard = new_guard(device)
+    ops.grad_norm(table, n_t, table[t_bytes:nbytes], n_c, table[nbytes:].view(torch.float64), max_norm, guard)
+    return table, n_t, table[t_bytes:nbytes], n_c, guard
+
+
+def grad_norm(parameters):
+    """The global L2 norm of the gradients of `parameters` (a tensor or an iterable; those without a .grad sit out) as a 0-dim fp32
+    device tensor: one dvc_grad_norm, nothing synchronised.  Raises while the stream is capturing."""
+    where = "dvc_amd.optim.grad_norm"
+    grads = _gradients(parameters, where, in_place=False)
+    if sum(g.numel() for g in grads) == 0:
+        return torch.zeros((), device=grads[0].device) if grads else torch.tensor(0.0)
+    guard = _functional_norm(grads, math.inf, where)[-1]
+    return guard_views(guard)[0]
+
+
+@torch.no_grad()
+def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=False, foreach=None):
+    """torch.nn.utils.clip_grad_norm_ on one dvc_grad_norm and one dvc_grad_scale: the gradients are multiplied in place by
+    min(1, max_norm / (norm + 1e-6)) and the norm comes back as a 0-dim fp32 device tensor.  Nothing is synchronised unless
+    `error_if_nonfinite` (one read of the flag).  Only the 2-norm; `foreach` is accepted and ignored (there is one path).
+    Non-finite gradients without `error_if_nonfinite` are scaled as torch scales them (include/dvc_hip.h, dvc_grad_scale)."""
+    where = "dvc_amd.optim.clip_grad_norm_"
+    if float(norm_type) != 2.0:
+        raise NotImplementedError(f"{where}: only norm_type=2 is supported by the HIP reduction (got {norm_type})")
+    if max_norm is None:
+        raise ValueError(f"{where}: `max_norm` must be a positive number (got None)")
+    max_norm = _checked_max_norm(max_norm, where)
+    grads = _gradients(parameters, where, in_place=True)
+    if sum(g.numel() for g in grads) == 0:
+        return torch.zeros((), device=grads[0].device) if grads else torch.tensor(0.0)
+    table, n_t, chunks, n_c, guard = _functional_norm(grads, max_norm, where)
+    if error_if_nonfinite and read_guard(guard)["found_inf"]:
+        raise RuntimeError(_NONFINITE_MESSAGE.format(float(norm_type)))
+    ops.grad_scale(table, n_t, chunks, n_c, guard)
+    return guard_views(guard)[0]
+
+
+class GuardedAdam(CapturableAdam):
+    """CapturableAdam whose step first measures its gradients, on four launches in a straight line over the resident tables:
+    dvc_grad_norm (two), dvc_adam_advance_guarded, dvc_adam_step_guarded.
+
+    `max_grad_norm` (keyword only; None: no clipping) is torch.nn.utils.clip_grad_norm_'s `max_norm`, over every tensor that has a
+    gradient in that step, all groups together: the step runs on min(1, max_grad_norm / (norm + 1e-6)) * g without writing `.grad`.
+    `skip_nonfinite` (default True): if any gradient holds a NaN or an Inf the step does nothing at all — parameters, moments and
+    every `step` count keep their bytes — and `skipped_steps` goes up by one.  With skip_nonfinite=False the same launches run but
+    the flag is never raised, and non-finite gradients do what they do to CapturableAdam.  With neither option active the result is
+    CapturableAdam's bit for bit (the multiply is by 1.0f).
+
+    Both options are attributes of the optimiser, not group keys: `state_dict()` is CapturableAdam's and loads into
+    torch.optim.Adam(capturable=True); pickling and deepcopy keep them.  An eager step reads them afresh; a replay has them baked in.
+
+    `last_grad_norm` (0-dim float32) and `skipped_steps` (0-dim int32) are device tensors that view the guard record, which is
+    allocated once, at construction, and lives as long as the optimiser; reading them synchronises, nothing in step() does.  The
+    norm's partial sums live behind the resident tables, in the same tensor, and are rebuilt with them.  A norm of finite
+    gradients that exceeds the fp32 range reads inf but does not skip the step: the flag and the coefficient come from the double.
+    The count is not part of state_dict(); a copy or an unpickled optimiser starts from 0.
+
+    Capture is CapturableAdam's, rule for rule; the captured sequence is [copy,] norm, finish, advance, step, with no branches."""
+
+    _name = "dvc_amd.optim.GuardedAdam"
+    _guarded = True
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, *, foreach=None,
+                 maximize=False, capturable=True, differentiable=False, fused=None, decoupled_weight_decay=False,
+                 max_grad_norm=None, skip_nonfinite=True):
+        _checked_max_norm(max_grad_norm, self._name)
+        self.max_grad_norm = max_grad_norm
+        self.skip_nonfinite = bool(skip_nonfinite)
+        super().__init__(params, lr, betas, eps, weight_decay, amsgrad, foreach=foreach, maximize=maximize, capturable=capturable,
+                         differentiable=differentiable, fused=fused, decoupled_weight_decay=decoupled_weight_decay)
+        self._ensure_guard()
+
+    def __getstate__(self):
+        state = super().__getstate__()
+        state["max_grad_norm"], state["skip_nonfinite"] = self.max_grad_norm, self.skip_nonfinite
+        return state
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        self.__dict__.setdefault("max_grad_norm", None)
+        self.__dict__.setdefault("skip_nonfinite", True)
+
+    def add_param_group(self, param_group):
+        super().add_param_group(param_group)
+        if "_dvc_spare" in self.__dict__:       # (not while the constructor is still adding its groups)
+            self._ensure_guard()
+
+    def _ensure_guard(self):
+        """The guard record, allocated and zeroed OUTSIDE any capture (a zeroing inside one would be replayed, count and all)."""
+        guard = self.__dict__.get("_dvc_guard")
+        if guard is not None:
+            return guard
+        device = next((p.device for group in self.param_groups for p in group["params"] if p.is_cuda), None)
+        if device is None:
+            return None
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"{self._name}: the guard record does not exist yet and the stream is capturing: every replay would "
+                               "zero it again; construct the optimiser (or take one eager step) before the capture")
+        guard = self.__dict__["_dvc_guard"] = new_guard(device)
+        self.__dict__["_dvc_guard_stream"] = ops._stream_handle()
+        return guard
+
+    def _guard_view(self, which):
+        guard = self._ensure_guard()
+        if guard is None:
+            raise RuntimeError(f"{self._name}: no parameter is a ROCm device tensor yet, so there is no guard record to read")
+        return guard_views(guard)[which]
+
+    @property
+    def last_grad_norm(self):
+        return self._guard_view(0)
+
+    @property
+    def skipped_steps(self):
+        return self._guard_view(1)
+
+    def _scratch_bytes(self, n_c):
+        return 8 * n_c
+
+    def _launch_resident(self, res, capturing):
+        if not res.n_c:         # only empty tensors: nothing to measure, nothing to skip
+            return super()._launch_resident(res, capturing)
+        guard = res.guard = self._ensure_guard()
+        if not capturing and ops._stream_handle() != self.__dict__["_dvc_guard_stream"]:
+            guard.record_stream(torch.cuda.current_stream())
+            self.__dict__["_dvc_guard_stream"] = ops._stream_handle()
+        max_norm = _checked_max_norm(self.max_grad_norm, self._name)
+        ops.grad_norm(res.table, res.n_t, res.chunks, res.n_c, res.scratch.view(torch.float64), max_norm, guard,
+                      keep_nonfinite=not self.skip_nonfinite)
+        ops.adam_advance_guarded(res.advance, res.table, res.n_t, guard)
+        ops.adam_step_guarded(res.table, res.n_t, res.chunks, res.n_c, guard)

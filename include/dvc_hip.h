@@ -831,6 +831,54 @@ typedef struct DvcAdamAdvance {
 } DvcAdamAdvance;       /* 40 bytes */
 int dvc_adam_advance(const DvcAdamAdvance* advance, DvcAdamTensor* tensors, int32_t n_tensors, dvcStream stream);
 
+/* The gradient guard (dvc_amd.optim.GuardedAdam, optim.grad_norm, optim.clip_grad_norm_): the global L2 norm of every gradient of
+ * the tensor table, clip_grad_norm_'s coefficient and a non-finite flag, kept in a 24-byte DEVICE record that the guarded advance
+ * and step obey — so a step replayed from a graph can clip its gradients and skip itself on a NaN or Inf with no host code.  All
+ * four entry points work on the tensor and chunk tables of dvc_adam_step.
+ * dvc_grad_norm, two launches; only g and n of a tensor record are read.  Stage 1 (256 threads, grid min(n_chunks, 2048),
+ *   grid-stride over the chunks): thread j of a chunk adds (double)g * (double)g — exact: the square of an fp32 value fits a double —
+ *   of its elements 4 (j + 256 r) + k (r = 0..3, k = 0..3) in that order, by 16-byte loads when g + start is 16-byte aligned and
+ *   the four lie inside the chunk, by dword loads otherwise (same values, same order); block_sum (csrc/reduce.h: butterfly in the
+ *   wave, the four waves in CHAIN order) combines the 256 doubles into partials[chunk], a function of the chunk's data alone.
+ *   Stage 2, one workgroup: thread j adds partials j, j + 256, ..., block_sum gives S, and thread 0 writes, with ordinary stores,
+ *     sumsq = S;  total_norm = (float)sqrt(S);  nonfinite = S is NaN or inf
+ *     clip_coef = nonfinite ? 1.0f : (float)min(1.0, max_norm / (sqrt(S) + 1e-6))      (in double: clip_grad_norm_'s formula;
+ *                                                                                      max_norm = +inf gives exactly 1.0f)
+ *     found_inf = nonfinite && !(flags & DVC_GRAD_NORM_KEEP_NONFINITE);   skipped += found_inf
+ *   The caller zeroes `skipped` once; every other field is overwritten.  With DVC_GRAD_NORM_KEEP_NONFINITE the flag stays 0 and the
+ *   coefficient 1.0f on non-finite gradients: the guarded step then does what dvc_adam_step does with them.  Finite gradients
+ *   whose norm exceeds the fp32 range report total_norm = inf with found_inf = 0, and clip_coef is still the finite value computed
+ *   from the double.  No atomics; the record and every partial are bit-reproducible and independent of what else is in the table.
+ *   `partials`: n_chunks doubles of scratch.
+ * dvc_adam_advance_guarded: dvc_adam_advance, except that with guard->found_inf set it touches nothing — `step` is not advanced and
+ *   the two columns are not rewritten.
+ * dvc_adam_step_guarded: dvc_adam_step, except that with guard->found_inf set it returns before any load or store, and otherwise
+ *   uses g' = clip_coef * g (one fp32 multiply, exact for 1.0f) in g's place.  g is never written.
+ * dvc_grad_scale: g *= c in place (g is written through the table's const pointer: the gradients are the caller's), for the
+ *   stand-alone clip_grad_norm_.  c = guard->clip_coef; with found_inf set it is what torch.nn.utils.clip_grad_norm_ (with
+ *   error_if_nonfinite=False) multiplies by: NaN when the norm is NaN (every gradient becomes NaN), 0 when it is inf (Inf elements
+ *   become NaN, the others 0).  One case differs from torch: max_norm = +inf with an infinite norm, where torch's inf / inf gives
+ *   NaN and the record no longer knows max_norm; 0 is used.  c == 1.0f stores nothing.
+ * All refuse before launching: a negative count; null tables or a null guard, or n_chunks == 0, with tensors present; dvc_grad_norm
+ * also a max_norm that is NaN or <= 0, unknown flags and null partials.  n_tensors == 0 is a successful no-op (the record is not
+ * written).  Nothing is allocated, copied or synchronised. */
+#define DVC_GRAD_NORM_KEEP_NONFINITE 1u
+typedef struct DvcGradGuard {
+    float total_norm;   /* (float)sqrt(sumsq) */
+    float clip_coef;    /* what the guarded step and dvc_grad_scale multiply g by */
+    int32_t found_inf;  /* 1: sumsq is NaN or inf, and the step is to be skipped */
+    int32_t skipped;    /* running count of found_inf */
+    double sumsq;       /* sum of g^2 over every tensor, in double */
+} DvcGradGuard;         /* 24 bytes */
+int dvc_grad_norm(const DvcAdamTensor* tensors, int32_t n_tensors, const DvcAdamChunk* chunks, int64_t n_chunks, double* partials,
+                  double max_norm, uint32_t flags, DvcGradGuard* guard, dvcStream stream);
+int dvc_adam_advance_guarded(const DvcAdamAdvance* advance, DvcAdamTensor* tensors, int32_t n_tensors, const DvcGradGuard* guard,
+                             dvcStream stream);
+int dvc_adam_step_guarded(const DvcAdamTensor* tensors, int32_t n_tensors, const DvcAdamChunk* chunks, int64_t n_chunks,
+                          const DvcGradGuard* guard, dvcStream stream);
+int dvc_grad_scale(const DvcAdamTensor* tensors, int32_t n_tensors, const DvcAdamChunk* chunks, int64_t n_chunks,
+                   const DvcGradGuard* guard, dvcStream stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Pixel losses: every term scale * mean_i(w * |x_i - t_i|^p), p in {1, 2}, of a training step on one fused reduction —
  * csrc/loss.hip, driven by dvc_amd/losses.py (train.py's mse_loss / l1_loss / weighted_mse_loss / weighted_l1_loss).  As for Adam,
