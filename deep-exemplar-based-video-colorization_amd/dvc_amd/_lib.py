@@ -82,6 +82,15 @@ class DvcLossChunk(ctypes.Structure):
     _fields_ = [("term", c_i32), ("reserved", c_i32), ("start", c_i64)]
 
 
+class DvcPlanTerm(ctypes.Structure):
+    _fields_ = [
+        ("x", ctypes.c_void_p), ("t", ctypes.c_void_p), ("w", ctypes.c_void_p), ("dx", ctypes.c_void_p), ("dt", ctypes.c_void_p),
+        ("n", c_i64), ("plane", c_i64), ("cpl", c_i64), ("p", c_i32), ("kind", c_i32),
+        ("t_scalar", ctypes.c_float), ("scale", ctypes.c_float),
+        ("y", ctypes.c_void_p), ("dy", ctypes.c_void_p), ("n_y", c_i64), ("c", ctypes.c_float), ("slot", c_i32),
+    ]
+
+
 # every symbol include/dvc_hip.h declares: name -> (restype, argtypes)
 _VP = ctypes.c_void_p
 SIGNATURES = {
@@ -222,6 +231,9 @@ SIGNATURES = {
     "dvc_grad_scale": (ctypes.c_int, [_VP, c_i32, _VP, c_i64, _VP, _VP]),
     "dvc_loss_fwd": (ctypes.c_int, [_VP, _VP, c_i32, _VP, c_i64, _VP, _VP, _VP]),
     "dvc_loss_bwd": (ctypes.c_int, [_VP, _VP, c_i32, _VP, c_i64, _VP, _VP, _VP]),
+    "dvc_loss_plan_check": (ctypes.c_int, [_VP, c_i32, c_i64, c_i64]),
+    "dvc_loss_plan_fwd": (ctypes.c_int, [_VP, c_i32, _VP, c_i64, c_i64, _VP, _VP, _VP]),
+    "dvc_loss_plan_bwd": (ctypes.c_int, [_VP, c_i32, _VP, c_i64, c_i64, _VP, _VP, _VP, _VP]),
 }
 # diagnostics for tools/ (include/dvc_hip.h, last section): exported by the -DDVC_DEBUG build only
 DEBUG_SIGNATURES = {

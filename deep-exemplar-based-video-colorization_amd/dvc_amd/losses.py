@@ -250,3 +250,288 @@ def weighted_mse_loss(input, target, weights):
 def weighted_l1_loss(input, target, weights):
     """(torch.abs(input - target) * weights.expand_as(input)).mean() — utils/util.py's weighted_l1_loss."""
     return _one("l1", input, target, weights)
+
+
+# ---- plans: resident tables, replayable, with the signed mean and the relativistic GAN term (csrc/loss_plan.hip)
+PLAN_TERM_DTYPE = np.dtype(_lib.DvcPlanTerm)
+PLAN_KINDS = {"l1": 1, "mse": 2, "mean": 3, "rel": 4}       # == DVC_LOSS_KIND_* of include/dvc_hip.h
+_PLAN_P = {1: 1, 2: 2, 3: 1, 4: 2}
+_REL = PLAN_KINDS["rel"]
+HINT_CHUNKS = 4096      # chunk records a spare sized from `n_terms_hint` has room for: 16 Mi elements over all terms
+
+
+def build_plan_tables(entries):
+    """The tables of one direction of a plan from `entries`, one (kind, x, t, w, dx, dt, n, plane, cpl, t_scalar, scale, y, dy, n_y,
+    c) per term: the kind number, five addresses, the count and geometry of a DvcLossTerm, the two scalars, and for a relativistic
+    term the addresses of y and dy, y's count and the constant (0 otherwise).  -> (PLAN_TERM_DTYPE array, CHUNK_DTYPE array, n_c,
+    n_yc): the chunk table holds the n_c chunks of every x, then the n_yc chunks of every relativistic term's y, both in term order
+    with the term's index in the plan; relativistic terms take the scratch slots 0, 1, ... in order.  Needs no device."""
+    terms = np.zeros(len(entries), dtype=PLAN_TERM_DTYPE)
+    slot = 0
+    for i, (kind, x, t, w, dx, dt, n, plane, cpl, ts, sc, y, dy, n_y, c) in enumerate(entries):
+        terms[i] = (x, t, w, dx, dt, n, plane, cpl, _PLAN_P.get(kind, 0), kind, ts, sc, y, dy, n_y, c, slot if kind == _REL else 0)
+        slot += kind == _REL
+    xc = chunk_table([e[6] for e in entries])
+    yc = chunk_table([e[13] if e[0] == _REL else 0 for e in entries])
+    return terms, np.concatenate([xc, yc]), len(xc), len(yc)
+
+
+def plan_fingerprint(entries):
+    """What a plan's resident tables were built from: per term its kind, addresses, counts, geometry and scalars — the entries
+    themselves, as a tuple.  Equal fingerprints <=> the tables a rebuild would write are the ones already on the device."""
+    return tuple(tuple(e) for e in entries)
+
+
+def _check_rel(where, x, y, c, scale):
+    """The refusals of a ("rel", x, y, c, scale) term that need no device, then the device ones; -> (x, y, float(c), float(scale))."""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError(f"{where}: input must be a tensor (got {type(x).__name__})")
+    if not isinstance(scale, numbers.Real) or isinstance(scale, bool):
+        raise TypeError(f"{where}: scale must be a Python number (got {type(scale).__name__})")
+    if not isinstance(c, numbers.Real) or isinstance(c, bool):
+        raise TypeError(f"{where}: c must be a Python number (got {type(c).__name__}); the term is (\"rel\", x, y, c, scale)")
+    if not isinstance(y, torch.Tensor):
+        raise TypeError(f"{where}: y must be a float32 device tensor (got {type(y).__name__})")
+    for name, v in (("input", x), ("y", y)):
+        if v.dtype != torch.float32:
+            raise TypeError(f"{where}: {name} must be float32 (got {v.dtype})")
+    if x.numel() == 0:
+        raise ValueError(f"{where}: the input has no elements (shape {tuple(x.shape)}); torch's mean of it would be NaN")
+    if y.numel() == 0:
+        raise ValueError(f"{where}: y has no elements (shape {tuple(y.shape)}); torch's mean of it would be NaN")
+    for name, v in (("input", x), ("y", y)):
+        if not v.is_cuda:
+            raise RuntimeError(f"{where}: {name} must be a ROCm device tensor; the HIP reduction has no CPU fallback")
+    if y.device != x.device:
+        raise RuntimeError(f"{where}: y lives on {y.device} but input on {x.device}")
+    return x, y, float(c), float(scale)
+
+
+class _PlanResident:
+    """One direction's tables on the device ([term records | chunk records | scratch]) and what they were built from."""
+    __slots__ = ("key", "table", "n", "n_c", "n_yc", "terms", "chunks", "scratch", "pinned", "stream", "captured")
+
+    def __init__(self, key, table, n, n_c, n_yc, pinned, stream):
+        t_bytes = n * PLAN_TERM_DTYPE.itemsize              # (112 n: the chunk table and the scratch stay 16-byte aligned)
+        c_end = t_bytes + (n_c + n_yc) * CHUNK_DTYPE.itemsize
+        self.key, self.table, self.n, self.n_c, self.n_yc = key, table, n, n_c, n_yc
+        self.terms, self.chunks = table[:t_bytes], table[t_bytes:c_end]
+        self.scratch = table[c_end:].view(torch.float64)    # (the forward's; empty for the backward's tables)
+        self.pinned = pinned        # the buffer a CAPTURED upload reads on every replay (None for an eager upload)
+        self.stream = stream        # the last stream it was used on
+        self.captured = False
+
+
+class _PlanFn(torch.autograd.Function):
+    """(plan, spec, *tensors) -> (total, values).  spec: per term (kind, scale, t_scalar, has_t, has_w, plane, cpl, c); tensors: per
+    term x, then t and w where present, or x and y for a relativistic term.  One ops.loss_plan_fwd, one ops.loss_plan_bwd."""
+
+    @staticmethod
+    def forward(ctx, plan, spec, *tensors):
+        entries, it = [], iter(tensors)
+        for kind, scale, t_scalar, has_t, has_w, plane, cpl, c in spec:
+            x = next(it)
+            if kind == _REL:
+                y = next(it)
+                entries.append((kind, x.data_ptr(), 0, 0, 0, 0, x.numel(), 1, 0, 0.0, scale, y.data_ptr(), 0, y.numel(), c))
+            else:
+                t = next(it) if has_t else None
+                w = next(it) if has_w else None
+                entries.append((kind, x.data_ptr(), _ptr(t), _ptr(w), 0, 0, x.numel(), plane, cpl, t_scalar, scale, 0, 0, 0, 0.0))
+        n, device = len(spec), tensors[0].device
+        res = plan._tables(0, entries, device)
+        out = torch.empty(n + 1, dtype=torch.float32, device=device)
+        ops.loss_plan_fwd(res.terms, n, res.chunks, res.n_c, res.n_yc, res.scratch, out)
+        plan._generation += 1
+        ctx.plan, ctx.spec, ctx.res, ctx.generation = plan, spec, res, plan._generation
+        ctx.save_for_backward(*tensors)
+        ctx.set_materialize_grads(False)
+        return out[n], out[:n]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_total, g_values):
+        tensors, need = ctx.saved_tensors, ctx.needs_input_grad[2:]
+        grads = [None] * len(tensors)
+        if g_total is None and g_values is None:
+            return (None, None, *grads)
+        plan, fwd = ctx.plan, ctx.res
+        if fwd.n_yc and plan._generation != ctx.generation:
+            raise RuntimeError("dvc_amd.losses.Plan: the plan was called again before this backward, and the sums a relativistic "
+                               "term's backward reads from the plan's scratch are the later call's; use one Plan per call site")
+        device = tensors[0].device
+        g_total = torch.zeros(1, dtype=torch.float32, device=device) if g_total is None else g_total.contiguous()
+        g_values = None if g_values is None else g_values.contiguous()
+        entries, i = [], 0
+        for kind, scale, t_scalar, has_t, has_w, plane, cpl, c in ctx.spec:
+            x, ix = tensors[i], i
+            i += 1
+            if need[ix]:
+                grads[ix] = torch.empty_like(x)
+            if kind == _REL:
+                y, iy = tensors[i], i
+                i += 1
+                if need[iy]:
+                    grads[iy] = torch.empty_like(y)
+                entries.append((kind, x.data_ptr(), 0, 0, _ptr(grads[ix]), 0, x.numel(), 1, 0, 0.0, scale, y.data_ptr(),
+                                _ptr(grads[iy]), y.numel(), c))
+                continue
+            t = w = None
+            dt = 0
+            if has_t:
+                t = tensors[i]
+                if need[i]:
+                    grads[i] = torch.empty_like(t)
+                    dt = grads[i].data_ptr()
+                i += 1
+            if has_w:
+                w = tensors[i]
+                i += 1
+            entries.append((kind, x.data_ptr(), _ptr(t), _ptr(w), _ptr(grads[ix]), dt, x.numel(), plane, cpl, t_scalar, scale,
+                            0, 0, 0, 0.0))
+        res = plan._tables(1, entries, device)
+        ops.loss_plan_bwd(res.terms, res.n, res.chunks, res.n_c, res.n_yc, fwd.scratch, g_total, g_values)
+        return (None, None, *grads)
+
+
+class Plan:
+    """A list of loss terms on tables that stay on the device: `total, values = plan(terms)` with `fused`'s return contract, where a
+    term is (kind, input, target, weights_or_None, scale) with kind in {"l1", "mse", "mean"} or ("rel", x, y, c, scale):
+
+      "l1", "mse"   scale * mean(w * |input - target|^p), with `fused`'s bits;
+      "mean"        scale * mean(w * (input - target)), signed; target and weights as for "l1";
+      "rel"         scale * mean(((x - mean(y)) - c)^2), the relativistic GAN term; x and y float32 device tensors of any shapes
+                    and sizes, both differentiable, c a Python number.
+
+    A call checks the terms as `fused` does (the same refusals by the same exception types; an unknown kind, a non-number c and a
+    y that is not a float32 device tensor or has no elements are refused too) and fingerprints kinds, addresses, counts, geometry
+    and scalars (`plan_fingerprint`).  If nothing moved since the tables were uploaded the forward is its launches and one
+    allocation, the outputs: no numpy, no copy.  The backward works the same way against tables of its own, which also carry the
+    dx / dt / dy addresses — it hits when the allocator hands the gradients the addresses of the step before.  If something moved,
+    that direction's tables are rebuilt, checked by dvc_loss_plan_check, and sent with one copy from a pinned buffer under
+    optim._Staging's discipline.  `uploads` counts those copies.
+
+    A call works under `torch.cuda.graph`; the rule is CapturableAdam's.  Tables uploaded during a capture are sent from a pinned
+    buffer of their own that is never rewritten, and resident tables a graph refers to live as long as the plan.  Pinned memory is
+    never allocated during a capture: two spares are kept, sized from `n_terms_hint` (room for that many terms and HINT_CHUNKS
+    chunks) or from the first eager call; without one a captured call raises a RuntimeError that says to call the plan eagerly
+    once.  A replay recomputes from whatever the SAME tensors then hold.
+
+    The sum a relativistic term's backward needs is left in the plan's scratch by the forward, so the backward of a call must run
+    before the plan is called again (it raises otherwise): one Plan per call site — one for the discriminator step, one for the
+    generator step.  Non-contiguous inputs are made contiguous in torch first, which moves them on every call."""
+
+    def __init__(self, n_terms_hint=None):
+        if n_terms_hint is not None and (not isinstance(n_terms_hint, numbers.Integral) or isinstance(n_terms_hint, bool)
+                                         or n_terms_hint < 1):
+            raise ValueError(f"dvc_amd.losses.Plan: n_terms_hint must be a positive integer or None (got {n_terms_hint!r})")
+        self._staging = optim._Staging()
+        self._resident = [None, None]       # forward, backward
+        self._captured = []                 # tables a graph refers to: alive as long as the plan
+        self._spares = []                   # pinned buffers for uploads that are themselves captured
+        self._spare_bytes = 0
+        self._generation = 0
+        self.uploads = 0
+        if n_terms_hint is not None:
+            self._spare_bytes = int(n_terms_hint) * PLAN_TERM_DTYPE.itemsize + HINT_CHUNKS * CHUNK_DTYPE.itemsize
+            self._ensure_spares()
+
+    def _ensure_spares(self):
+        """Two pinned buffers (a capture may upload both directions), allocated OUTSIDE any capture."""
+        if not self._spare_bytes or not torch.cuda.is_available() or torch.cuda.is_current_stream_capturing():
+            return
+        self._spares = [s for s in self._spares if s.numel() >= self._spare_bytes]
+        while len(self._spares) < 2:
+            self._spares.append(torch.empty(self._spare_bytes, dtype=torch.uint8, pin_memory=True))
+
+    def _tables(self, which, entries, device):
+        """The resident tables of direction `which` for `entries`: the ones on the device if the fingerprint is theirs, else rebuilt."""
+        key = plan_fingerprint(entries)
+        capturing = torch.cuda.is_current_stream_capturing()
+        res = self._resident[which]
+        if res is None or res.key != key or res.table.device != device:
+            res = self._upload(which, key, entries, device, capturing)
+        stream = ops._stream_handle()
+        if capturing:
+            if not res.captured:        # a graph refers to these tables from now on: they live as long as the plan
+                res.captured = True
+                self._captured.append(res)
+        else:
+            if stream != res.stream:
+                if not res.captured:    # (allocated on another stream: the allocator must not reuse it under this one's launches)
+                    res.table.record_stream(torch.cuda.current_stream())
+                res.stream = stream
+            if len(self._spares) < 2:
+                self._ensure_spares()
+        return res
+
+    def _upload(self, which, key, entries, device, capturing):
+        """Rebuild one direction's tables, check them, and send them to a fresh table tensor with one host-to-device copy."""
+        terms, chunks, n_c, n_yc = build_plan_tables(entries)
+        ops.loss_plan_check(terms, n_c, n_yc)
+        t_bytes, nbytes = terms.nbytes, terms.nbytes + chunks.nbytes
+        st = None
+        if capturing:       # a buffer of its own, never rewritten: the replay's copy node reads it again
+            pinned = next((s for s in self._spares if s.numel() >= nbytes), None)
+            if pinned is None:
+                raise RuntimeError("dvc_amd.losses.Plan: the tables have to be uploaded and the stream is capturing, but no pinned "
+                                   "buffer of their size was set aside (pinned memory is not allocated during a capture); call the "
+                                   "plan eagerly once with these terms before the capture, or pass n_terms_hint")
+            self._spares.remove(pinned)
+        else:
+            st = self._staging
+            slot = st.slot = 1 - st.slot
+            if st.event[slot] is not None:
+                st.event[slot].synchronize()        # the copy that last read this buffer (two uploads ago) has run
+            if st.buf[slot] is None or st.buf[slot].numel() < nbytes:
+                st.buf[slot] = torch.empty(nbytes + nbytes // 4, dtype=torch.uint8, pin_memory=True)
+            pinned = st.buf[slot]
+            self._spare_bytes = max(self._spare_bytes, nbytes)
+        host = pinned.numpy()
+        host[:t_bytes].view(PLAN_TERM_DTYPE)[:] = terms
+        host[t_bytes:nbytes].view(CHUNK_DTYPE)[:] = chunks
+        scratch = 8 * ops.loss_plan_scratch_doubles(len(terms), n_c, n_yc) if which == 0 else 0
+        table = torch.empty(nbytes + scratch, dtype=torch.uint8, device=device)
+        table[:nbytes].copy_(pinned[:nbytes], non_blocking=True)
+        if st is not None:
+            if st.event[slot] is None:
+                st.event[slot] = torch.cuda.Event()
+            st.event[slot].record()
+        self.uploads += 1
+        res = self._resident[which] = _PlanResident(key, table, len(terms), n_c, n_yc, pinned if capturing else None,
+                                                    ops._stream_handle())
+        return res
+
+    def __call__(self, terms):
+        where = "dvc_amd.losses.Plan"
+        terms = list(terms)
+        if not terms:
+            raise ValueError(f"{where}: no terms")
+        for k, term in enumerate(terms):
+            if not isinstance(term, (tuple, list)) or len(term) != 5:
+                raise ValueError(f"{where}: term {k} is not (kind, input, target, weights_or_None, scale) or (\"rel\", x, y, c, scale)")
+        spec, tensors = [], []
+        for k, (kind, a, b, c, scale) in enumerate(terms):
+            at = f"{where}: term {k}"
+            if not isinstance(kind, str) or kind not in PLAN_KINDS:
+                raise ValueError(f"{at}: kind must be one of 'l1', 'mse', 'mean', 'rel' (got {kind!r})")
+            if kind == "rel":
+                x, y, cc, sc = _check_rel(at, a, b, c, scale)
+                spec.append((_REL, sc, 0.0, False, False, 1, 0, cc))
+                tensors += [x.contiguous(), y.contiguous()]
+            else:
+                T = _check_term(at, "l1" if kind == "mean" else kind, a, b, c, scale)
+                spec.append((PLAN_KINDS[kind], T.scale, T.t_scalar, T.t is not None, T.w is not None, T.plane, T.cpl, 0.0))
+                tensors += [v.contiguous() for v in (T.x, T.t, T.w) if v is not None]       # (a no-op for a contiguous tensor)
+        dev = ops._current_device()
+        for v in tensors:
+            if v.device.index != dev:
+                raise RuntimeError(f"{where}: a tensor lives on {v.device} but the current device is cuda:{dev}; call "
+                                   "torch.cuda.set_device / use torch.cuda.device(...)")
+        return _PlanFn.apply(self, tuple(spec), *tensors)
+
+
+def relativistic_loss(x, y, c):
+    """torch.mean((x - torch.mean(y) - c) ** 2) — one half of train.py's relativistic GAN objective — as a one-term Plan of its own
+    (so: eager only, and tables uploaded on every call; a training step keeps a Plan)."""
+    return Plan()([("rel", x, y, c, 1.0)])[0]

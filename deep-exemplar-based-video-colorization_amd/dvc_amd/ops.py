@@ -1970,3 +1970,55 @@ def loss_bwd(term_table, term_table_host, n_terms, chunk_table, n_chunks, grad_t
         raise RuntimeError(f"dvc_amd: `grad_total` must hold 1 float and `grad_values` {n_terms}")
     _lib.check(lib.dvc_loss_bwd(_p(term_table), _p(term_table_host), n_terms, _p(chunk_table), n_chunks, _p(grad_total),
                                 _p(grad_values), _stream()), "dvc_loss_bwd")
+
+
+# ---- loss plans (csrc/loss_plan.hip; dvc_amd.losses.Plan owns the resident tables)
+def loss_plan_scratch_doubles(n_terms, n_chunks, n_ychunks):
+    """DVC_LOSS_PLAN_SCRATCH of include/dvc_hip.h: [partials | partials of sum d | partials of y | per slot {m, sum d}]."""
+    return 2 * n_chunks + n_ychunks + 2 * n_terms
+
+
+def loss_plan_check(terms_host, n_chunks, n_ychunks):
+    """dvc_loss_plan_check: every refusal of a plan's term table, from its HOST copy (a numpy array of DvcPlanTerm records);
+    no device is touched and nothing is launched."""
+    lib = _lib.load()
+    if terms_host.dtype.itemsize != ctypes.sizeof(_lib.DvcPlanTerm) or not terms_host.flags["C_CONTIGUOUS"]:
+        raise RuntimeError("dvc_amd: `terms_host` must be a contiguous array of DvcPlanTerm records")
+    _lib.check(lib.dvc_loss_plan_check(ctypes.c_void_p(terms_host.ctypes.data), len(terms_host), n_chunks, n_ychunks),
+               "dvc_loss_plan_check")
+
+
+def _need_plan_tables(term_table, n_terms, chunk_table, n_chunks, n_ychunks, scratch):
+    _need_table(term_table, "term_table", n_terms * ctypes.sizeof(_lib.DvcPlanTerm))
+    _need_table(chunk_table, "chunk_table", (n_chunks + n_ychunks) * ctypes.sizeof(_lib.DvcLossChunk))
+    need = loss_plan_scratch_doubles(n_terms, n_chunks, n_ychunks)
+    if (not isinstance(scratch, torch.Tensor) or not scratch.is_cuda or scratch.dtype != torch.float64 or not scratch.is_contiguous()
+            or scratch.numel() < need):
+        raise RuntimeError(f"dvc_amd: `scratch` must be a contiguous float64 device tensor of at least {need} elements; the HIP path "
+                           "has no CPU fallback")
+
+
+def loss_plan_fwd(term_table, n_terms, chunk_table, n_chunks, n_ychunks, scratch, values):
+    """dvc_loss_plan_fwd: two launches (four with a relativistic term) that reduce every term of the device-resident tables —
+    uint8 device tensors that hold n_terms DvcPlanTerm and n_chunks + n_ychunks DvcLossChunk records, checked by loss_plan_check
+    when they were built — into `values` (float32, n_terms + 1: the terms, then the total); `scratch`: loss_plan_scratch_doubles."""
+    lib = _lib.load()
+    _need_plan_tables(term_table, n_terms, chunk_table, n_chunks, n_ychunks, scratch)
+    _need(values, "values")
+    if values.numel() < n_terms + 1:
+        raise RuntimeError(f"dvc_amd: `values` must hold {n_terms + 1} floats")
+    _lib.check(lib.dvc_loss_plan_fwd(_p(term_table), n_terms, _p(chunk_table), n_chunks, n_ychunks, _p(scratch), _p(values),
+                                     _stream()), "dvc_loss_plan_fwd")
+
+
+def loss_plan_bwd(term_table, n_terms, chunk_table, n_chunks, n_ychunks, scratch, grad_total, grad_values=None):
+    """dvc_loss_plan_bwd: ONE launch that writes dx / dt / dy of every term of the tables (those of the forward, with the gradient
+    addresses filled in) from the device scalars `grad_total` and `grad_values`; `scratch` is the one the forward wrote."""
+    lib = _lib.load()
+    _need_plan_tables(term_table, n_terms, chunk_table, n_chunks, n_ychunks, scratch)
+    _need(grad_total, "grad_total")
+    _need(grad_values, "grad_values")
+    if grad_total.numel() < 1 or (grad_values is not None and grad_values.numel() < n_terms):
+        raise RuntimeError(f"dvc_amd: `grad_total` must hold 1 float and `grad_values` {n_terms}")
+    _lib.check(lib.dvc_loss_plan_bwd(_p(term_table), n_terms, _p(chunk_table), n_chunks, n_ychunks, _p(scratch), _p(grad_total),
+                                     _p(grad_values), _stream()), "dvc_loss_plan_bwd")

@@ -928,6 +928,69 @@ int dvc_loss_fwd(const DvcLossTerm* terms, const DvcLossTerm* terms_host, int32_
 int dvc_loss_bwd(const DvcLossTerm* terms, const DvcLossTerm* terms_host, int32_t n_terms, const DvcLossChunk* chunks,
                  int64_t n_chunks, const float* grad_total, const float* grad_values, dvcStream stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Loss plans: the terms above and two more kinds on RESIDENT tables, so that a call whose tensors did not move is launches and
+ * nothing else and can be replayed from a captured graph — csrc/loss_plan.hip, driven by dvc_amd.losses.Plan.  The element and
+ * chunk code of kinds 1 and 2 is the one dvc_loss_fwd / dvc_loss_bwd run (csrc/loss_chunk.h), so their values and gradients have
+ * dvc_loss_fwd's bits.
+ *   kind 1 (L1), 2 (MSE): scale * mean(w * |x - t|^p) with p == kind, exactly as above.
+ *   kind 3 (MEAN): v_i = w_i * (x_i - t_i), signed; t and w as above; dx_i = c_k * w_i, dt_i = -dx_i.  p is 1.
+ *   kind 4 (REL), the relativistic GAN term scale * mean_i(((x_i - mean(y)) - c)^2): y is n_y floats of its own (n_y != n allowed),
+ *     t and w are NULL, p is 2.  m = (float)(S_y / n_y) with S_y the double sum of y in the order below; d_i = (x_i - m) - c, two
+ *     fp32 subtractions; v_i = d_i * d_i.  dx_i = (2 c_k) * d_i;  dy_j = (float)(-(double)(2 c_k) * (sum_i d_i) / n_y), the same for
+ *     every j, with sum_i d_i the double the FORWARD left in the scratch: the backward does not reduce again.
+ * `chunks` holds n_chunks records that cut the x of every term, terms in order (as for dvc_loss_fwd), and behind them n_ychunks
+ * records that cut the y of every REL term the same way, terms in order.  `scratch`, DVC_LOSS_PLAN_SCRATCH doubles the caller
+ * owns, is [n_chunks partials | n_chunks partials of sum d | n_ychunks partials of y | per slot {m, sum d}]; a REL term names its
+ * slot (0 <= slot < n_terms, no two REL terms the same one).
+ * dvc_loss_plan_check, HOST only, nothing launched and no device touched: every refusal, decided from the host copy of the term
+ * table at the time the tables are built — a resident table cannot be validated without a synchronising copy, so the launch
+ * entry points take device tables only and check nothing but null pointers and counts.  It refuses what dvc_loss_fwd refuses
+ * (negative counts, a null table, n_chunks == 0 or != sum ceil(n_k / DVC_LOSS_CHUNK), n <= 0, null x, the plane / cpl rules) and
+ * kind outside 1..4; p that does not belong to the kind; REL with null y, n_y <= 0, a t or a w, or a slot outside [0, n_terms) or
+ * used twice; another kind with a y, a dy or n_y != 0; n_ychunks != sum over REL terms of ceil(n_y / DVC_LOSS_CHUNK).
+ * A C caller must have had dvc_loss_plan_check accept the host copy of exactly these tables with exactly these n_terms, n_chunks and
+ * n_ychunks before it passes them to the two launch entry points: those take the counts on trust, size their grids from them and
+ * index `chunks` ((n_chunks + n_ychunks) records) and `scratch` (DVC_LOSS_PLAN_SCRATCH doubles) by them.
+ * dvc_loss_plan_fwd, two launches, four with a REL term (n_ychunks > 0), a straight line on `stream`:
+ *   stage 0a  per y chunk, thread j adds (double)y of elements 4 (j + 256 r) + k in that order, block_sum (CHAIN) -> its partial;
+ *   stage 0b  one workgroup: per REL term, thread j adds the term's y partials j, j + 256, ..., block_sum -> S_y; m -> its slot;
+ *   stage 1   per x chunk as dvc_loss_fwd; a REL chunk reads m from its slot and accumulates two doubles, sum d^2 and sum d;
+ *   stage 2   one workgroup: values[k] = (float)(S_k * scale_k / n_k) and values[n_terms] from the same doubles in term order,
+ *             dvc_loss_fwd's rule; a REL term's sum d (its partials j, j + 256, ..., block_sum) -> its slot.
+ *   Every partial depends on its chunk's data alone (a REL chunk's also on m, a function of y alone): a term's value is
+ *   bit-identical alone and inside any plan.
+ * dvc_loss_plan_bwd, one launch over the n_chunks + n_ychunks chunks; c_k from device memory as in dvc_loss_bwd.
+ * No atomics; nothing is allocated, copied or synchronised.  n_terms == 0 is a successful no-op. */
+#define DVC_LOSS_KIND_L1 1
+#define DVC_LOSS_KIND_MSE 2
+#define DVC_LOSS_KIND_MEAN 3
+#define DVC_LOSS_KIND_REL 4
+#define DVC_LOSS_PLAN_SCRATCH(n_terms, n_chunks, n_ychunks) (2 * (n_chunks) + (n_ychunks) + 2 * (n_terms))
+typedef struct DvcPlanTerm {
+    const float* x;     /* the first 80 bytes are DvcLossTerm's, with `kind` in the place of its reserved field */
+    const float* t;
+    const float* w;
+    float* dx;
+    float* dt;
+    int64_t n;
+    int64_t plane;
+    int64_t cpl;
+    int32_t p;          /* 1 for kinds 1 and 3, 2 for kinds 2 and 4 */
+    int32_t kind;       /* DVC_LOSS_KIND_* */
+    float t_scalar, scale;
+    const float* y;     /* REL: the tensor whose mean is subtracted; NULL otherwise */
+    float* dy;          /* backward, REL: gradient to y, or NULL */
+    int64_t n_y;        /* REL: elements of y; 0 otherwise */
+    float c;            /* REL: the constant */
+    int32_t slot;       /* REL: index of the term's {m, sum d} pair in the scratch */
+} DvcPlanTerm;          /* 112 bytes */
+int dvc_loss_plan_check(const DvcPlanTerm* terms_host, int32_t n_terms, int64_t n_chunks, int64_t n_ychunks);
+int dvc_loss_plan_fwd(const DvcPlanTerm* terms, int32_t n_terms, const DvcLossChunk* chunks, int64_t n_chunks, int64_t n_ychunks,
+                      double* scratch, float* values, dvcStream stream);
+int dvc_loss_plan_bwd(const DvcPlanTerm* terms, int32_t n_terms, const DvcLossChunk* chunks, int64_t n_chunks, int64_t n_ychunks,
+                      const double* scratch, const float* grad_total, const float* grad_values, dvcStream stream);
+
 #ifdef DVC_DEBUG
 /* ------------------------------------------------------------------------------------------------
  * Diagnostics for the timing probes under tools/ — ONLY in a -DDVC_DEBUG build (`make -C csrc DEBUG=1` ->
