@@ -6,10 +6,9 @@ scale * mean(w * |input - target|^p), p in {1, 2} — with ONE dvc_loss_fwd call
 The four helpers are `fused` with a one-row table, and a term's value is bit-identical whether it is computed alone or inside any
 `fused` call: the kernel's partial sums depend on the term's data alone.  Values and gradients are bit-reproducible from run to run.
 
-Per call the host writes the term table and the chunk table into a pinned staging buffer, sends them with one host-to-device copy on
-the current stream and launches; two staging buffers alternate, each behind an event recorded after its copy (dvc_amd.optim's
-scheme, and its chunk table).  The tables carry addresses, so a call cannot be replayed from a captured graph: it raises while the
-current stream is capturing.
+Per call the host sends the term table and the chunk table (dvc_amd.optim's) with one host-to-device copy on the current stream and
+launches; the staging buffers, and `Plan`'s resident tables, follow dvc_amd.tables, where the discipline is described once.  The
+tables carry addresses, so a call cannot be replayed from a captured graph: it raises while the current stream is capturing.
 
 What is not done is refused by name: CPU tensors (no CPU fallback), non-fp32, weights that require grad (the mask is data in
 train.py), broadcasts other than a Python-number target and a [B,1,H,W] weight, zero-element inputs.  Non-contiguous inputs are made
@@ -21,7 +20,7 @@ import numpy as np
 import torch
 from torch.autograd.function import once_differentiable
 
-from . import _lib, ops, optim
+from . import _lib, ops, optim, tables
 
 CHUNK = 4096  # elements per chunk == DVC_LOSS_CHUNK of include/dvc_hip.h (tests/test_losses_host.py holds the two together)
 TERM_DTYPE = np.dtype(_lib.DvcLossTerm)
@@ -105,6 +104,7 @@ def _check_term(where, kind, x, target, weights, scale):
 
 # ---- one call: tables through the staging buffers, one copy, the launch(es)
 _staging = {}       # device index -> optim._Staging
+_refuse_capture = optim._refuse_capture     # (where): "... its tables carry the tensors' addresses ..."
 
 
 def _send(entries, device):
@@ -113,33 +113,9 @@ def _send(entries, device):
     st = _staging.get(device.index)
     if st is None:
         st = _staging[device.index] = optim._Staging()
-    counts = tuple(e[5] for e in entries)
-    n_c = sum((n + CHUNK - 1) // CHUNK for n in counts)
-    t_bytes, c_bytes = len(entries) * TERM_DTYPE.itemsize, n_c * CHUNK_DTYPE.itemsize       # (80 n: the chunk table stays 16-byte aligned)
-    nbytes = t_bytes + c_bytes
-    slot = st.slot = 1 - st.slot
-    if st.event[slot] is not None:
-        st.event[slot].synchronize()        # the copy that last read this buffer (two calls ago) has run
-    if st.buf[slot] is None or st.buf[slot].numel() < nbytes:
-        st.buf[slot] = torch.empty(nbytes + nbytes // 4, dtype=torch.uint8, pin_memory=True)
-        st.counts[slot] = None
-    host = st.buf[slot].numpy()
-    host[:t_bytes].view(TERM_DTYPE)[:] = np.array([e[:9] + (0,) + e[9:] for e in entries], dtype=TERM_DTYPE)
-    if st.counts[slot] != counts:
-        host[t_bytes:nbytes].view(CHUNK_DTYPE)[:] = chunk_table(counts)
-        st.counts[slot] = counts
-    table = torch.empty(nbytes, dtype=torch.uint8, device=device)       # (freed on return: the allocator reuses it in stream order)
-    table.copy_(st.buf[slot][:nbytes], non_blocking=True)
-    if st.event[slot] is None:
-        st.event[slot] = torch.cuda.Event()
-    st.event[slot].record()
-    return table, st.buf[slot], t_bytes, n_c
-
-
-def _refuse_capture(where):
-    if torch.cuda.is_initialized() and torch.cuda.is_current_stream_capturing():        # before anything is allocated or launched
-        raise RuntimeError(f"{where} cannot be captured into a graph: its tables carry the tensors' addresses and are launch-time "
-                           "data; call it outside the capture")
+    terms = np.array([e[:9] + (0,) + e[9:] for e in entries], dtype=TERM_DTYPE)
+    table, host, n_c = optim._send(st, terms, tuple(e[5] for e in entries), device)      # (one chunk table serves both: above)
+    return table, host, terms.nbytes, n_c
 
 
 def _ptr(t):
@@ -203,28 +179,41 @@ class _Fused(torch.autograd.Function):
         return (None, *grads)
 
 
+def _checked_terms(where, terms, shape, row):
+    """The checks `fused` and `Plan` share, in their order: a non-empty list of 5-tuples (`shape` is how the message spells one);
+    per term `row(at, *term)` -> (its spec row, its tensors, None for an absent one), which refuses what it refuses; the tensors
+    made contiguous; all of them on the current device.  -> (spec tuple, tensor list)"""
+    terms = list(terms)
+    if not terms:
+        raise ValueError(f"{where}: no terms")
+    for k, term in enumerate(terms):
+        if not isinstance(term, (tuple, list)) or len(term) != 5:
+            raise ValueError(f"{where}: term {k} is not {shape}")
+    spec, tensors = [], []
+    for k, term in enumerate(terms):
+        one, used = row(f"{where}: term {k}", *term)
+        spec.append(one)
+        tensors += [v.contiguous() for v in used if v is not None]      # (a no-op for a contiguous tensor)
+    dev = ops._current_device()
+    for v in tensors:
+        if v.device.index != dev:
+            raise RuntimeError(f"{where}: a tensor lives on {v.device} but the current device is cuda:{dev}; call "
+                               "torch.cuda.set_device / use torch.cuda.device(...)")
+    return tuple(spec), tensors
+
+
+def _fused_row(at, *term):
+    T = _check_term(at, *term)
+    return (T.p, T.scale, T.t_scalar, T.t is not None, T.w is not None, T.plane, T.cpl), (T.x, T.t, T.w)
+
+
 def fused(terms):
     """terms: a list of (kind, input, target, weights_or_None, scale), kind in {"mse", "l1"} -> (total, values): the 0-dim sum of the
     terms and the [len(terms)] tensor of the terms, scale_k * mean(w * |input - target|^p), both differentiable in every input and
     target that requires grad.  One forward call and one backward call of the library serve every term."""
-    terms = list(terms)
-    if not terms:
-        raise ValueError("dvc_amd.losses.fused: no terms")
-    for k, term in enumerate(terms):
-        if not isinstance(term, (tuple, list)) or len(term) != 5:
-            raise ValueError(f"dvc_amd.losses.fused: term {k} is not (kind, input, target, weights_or_None, scale)")
-    spec, tensors = [], []
-    for k, term in enumerate(terms):
-        T =_check_term(f"dvc_amd.losses.fused: term {k}", *term)
-        spec.append((T.p, T.scale, T.t_scalar, T.t is not None, T.w is not None, T.plane, T.cpl))
-        tensors += [v.contiguous() for v in (T.x, T.t, T.w) if v is not None]       # (a no-op for a contiguous tensor)
-    dev = ops._current_device()
-    for v in tensors:
-        if v.device.index != dev:
-            raise RuntimeError(f"dvc_amd.losses.fused: a tensor lives on {v.device} but the current device is cuda:{dev}; call "
-                               "torch.cuda.set_device / use torch.cuda.device(...)")
+    spec, tensors = _checked_terms("dvc_amd.losses.fused", terms, "(kind, input, target, weights_or_None, scale)", _fused_row)
     _refuse_capture("dvc_amd.losses.fused")
-    return _Fused.apply(tuple(spec), *tensors)
+    return _Fused.apply(spec, *tensors)
 
 
 def _one(kind, input, target, weights):
@@ -307,19 +296,25 @@ def _check_rel(where, x, y, c, scale):
     return x, y, float(c), float(scale)
 
 
-class _PlanResident:
-    """One direction's tables on the device ([term records | chunk records | scratch]) and what they were built from."""
-    __slots__ = ("key", "table", "n", "n_c", "n_yc", "terms", "chunks", "scratch", "pinned", "stream", "captured")
+def _plan_row(at, kind, a, b, c, scale):
+    if not isinstance(kind, str) or kind not in PLAN_KINDS:
+        raise ValueError(f"{at}: kind must be one of 'l1', 'mse', 'mean', 'rel' (got {kind!r})")
+    if kind == "rel":
+        x, y, cc, sc = _check_rel(at, a, b, c, scale)
+        return (_REL, sc, 0.0, False, False, 1, 0, cc), (x, y)
+    T = _check_term(at, "l1" if kind == "mean" else kind, a, b, c, scale)
+    return (PLAN_KINDS[kind], T.scale, T.t_scalar, T.t is not None, T.w is not None, T.plane, T.cpl, 0.0), (T.x, T.t, T.w)
 
-    def __init__(self, key, table, n, n_c, n_yc, pinned, stream):
-        t_bytes = n * PLAN_TERM_DTYPE.itemsize              # (112 n: the chunk table and the scratch stay 16-byte aligned)
-        c_end = t_bytes + (n_c + n_yc) * CHUNK_DTYPE.itemsize
-        self.key, self.table, self.n, self.n_c, self.n_yc = key, table, n, n_c, n_yc
-        self.terms, self.chunks = table[:t_bytes], table[t_bytes:c_end]
-        self.scratch = table[c_end:].view(torch.float64)    # (the forward's; empty for the backward's tables)
-        self.pinned = pinned        # the buffer a CAPTURED upload reads on every replay (None for an eager upload)
-        self.stream = stream        # the last stream it was used on
-        self.captured = False
+
+class _PlanResident(tables.Resident):
+    """One direction's tables on the device ([term records | chunk records | scratch]) and what they were built from."""
+    __slots__ = ("n", "n_c", "n_yc", "terms", "chunks", "scratch")
+
+    def __init__(self, key, table, c_at, end, n, n_c, n_yc, pinned, stream):
+        super().__init__(key, table, pinned, stream)
+        self.n, self.n_c, self.n_yc = n, n_c, n_yc
+        self.terms, self.chunks = table[:c_at], table[c_at:end]
+        self.scratch = table[end:].view(torch.float64)      # (the forward's; empty for the backward's tables)
 
 
 class _PlanFn(torch.autograd.Function):
@@ -409,13 +404,12 @@ class Plan:
     allocation, the outputs: no numpy, no copy.  The backward works the same way against tables of its own, which also carry the
     dx / dt / dy addresses — it hits when the allocator hands the gradients the addresses of the step before.  If something moved,
     that direction's tables are rebuilt, checked by dvc_loss_plan_check, and sent with one copy from a pinned buffer under
-    optim._Staging's discipline.  `uploads` counts those copies.
+    tables.Staging's discipline.  `uploads` counts those copies.
 
-    A call works under `torch.cuda.graph`; the rule is CapturableAdam's.  Tables uploaded during a capture are sent from a pinned
-    buffer of their own that is never rewritten, and resident tables a graph refers to live as long as the plan.  Pinned memory is
-    never allocated during a capture: two spares are kept, sized from `n_terms_hint` (room for that many terms and HINT_CHUNKS
-    chunks) or from the first eager call; without one a captured call raises a RuntimeError that says to call the plan eagerly
-    once.  A replay recomputes from whatever the SAME tensors then hold.
+    A call works under `torch.cuda.graph`; the rule is CapturableAdam's and the tables are kept as dvc_amd.tables says.  Pinned
+    memory is never allocated during a capture: two spares are kept, sized from `n_terms_hint` (room for that many terms and
+    HINT_CHUNKS chunks) or from the first eager call; without one a captured call raises a RuntimeError that says to call the plan
+    eagerly once.  A replay recomputes from whatever the SAME tensors then hold.
 
     The sum a relativistic term's backward needs is left in the plan's scratch by the forward, so the backward of a call must run
     before the plan is called again (it raises otherwise): one Plan per call site — one for the discriminator step, one for the
@@ -451,26 +445,16 @@ class Plan:
         res = self._resident[which]
         if res is None or res.key != key or res.table.device != device:
             res = self._upload(which, key, entries, device, capturing)
-        stream = ops._stream_handle()
-        if capturing:
-            if not res.captured:        # a graph refers to these tables from now on: they live as long as the plan
-                res.captured = True
-                self._captured.append(res)
-        else:
-            if stream != res.stream:
-                if not res.captured:    # (allocated on another stream: the allocator must not reuse it under this one's launches)
-                    res.table.record_stream(torch.cuda.current_stream())
-                res.stream = stream
-            if len(self._spares) < 2:
-                self._ensure_spares()
+        res.use(self._captured, capturing, ops._stream_handle())
+        if not capturing and len(self._spares) < 2:
+            self._ensure_spares()
         return res
 
     def _upload(self, which, key, entries, device, capturing):
         """Rebuild one direction's tables, check them, and send them to a fresh table tensor with one host-to-device copy."""
         terms, chunks, n_c, n_yc = build_plan_tables(entries)
         ops.loss_plan_check(terms, n_c, n_yc)
-        t_bytes, nbytes = terms.nbytes, terms.nbytes + chunks.nbytes
-        st = None
+        nbytes = terms.nbytes + chunks.nbytes
         if capturing:       # a buffer of its own, never rewritten: the replay's copy node reads it again
             pinned = next((s for s in self._spares if s.numel() >= nbytes), None)
             if pinned is None:
@@ -479,56 +463,23 @@ class Plan:
                                    "plan eagerly once with these terms before the capture, or pass n_terms_hint")
             self._spares.remove(pinned)
         else:
-            st = self._staging
-            slot = st.slot = 1 - st.slot
-            if st.event[slot] is not None:
-                st.event[slot].synchronize()        # the copy that last read this buffer (two uploads ago) has run
-            if st.buf[slot] is None or st.buf[slot].numel() < nbytes:
-                st.buf[slot] = torch.empty(nbytes + nbytes // 4, dtype=torch.uint8, pin_memory=True)
-            pinned = st.buf[slot]
+            slot = self._staging.acquire(nbytes)
+            pinned = self._staging.buf[slot]
             self._spare_bytes = max(self._spare_bytes, nbytes)
-        host = pinned.numpy()
-        host[:t_bytes].view(PLAN_TERM_DTYPE)[:] = terms
-        host[t_bytes:nbytes].view(CHUNK_DTYPE)[:] = chunks
+        (_, c_at), _ = tables.pack(pinned.numpy(), [terms, chunks])
         scratch = 8 * ops.loss_plan_scratch_doubles(len(terms), n_c, n_yc) if which == 0 else 0
-        table = torch.empty(nbytes + scratch, dtype=torch.uint8, device=device)
-        table[:nbytes].copy_(pinned[:nbytes], non_blocking=True)
-        if st is not None:
-            if st.event[slot] is None:
-                st.event[slot] = torch.cuda.Event()
-            st.event[slot].record()
+        table = tables.upload(pinned, nbytes, device, scratch)
+        if not capturing:
+            self._staging.sent(slot)
         self.uploads += 1
-        res = self._resident[which] = _PlanResident(key, table, len(terms), n_c, n_yc, pinned if capturing else None,
+        res = self._resident[which] = _PlanResident(key, table, c_at, nbytes, len(terms), n_c, n_yc, pinned if capturing else None,
                                                     ops._stream_handle())
         return res
 
     def __call__(self, terms):
-        where = "dvc_amd.losses.Plan"
-        terms = list(terms)
-        if not terms:
-            raise ValueError(f"{where}: no terms")
-        for k, term in enumerate(terms):
-            if not isinstance(term, (tuple, list)) or len(term) != 5:
-                raise ValueError(f"{where}: term {k} is not (kind, input, target, weights_or_None, scale) or (\"rel\", x, y, c, scale)")
-        spec, tensors = [], []
-        for k, (kind, a, b, c, scale) in enumerate(terms):
-            at = f"{where}: term {k}"
-            if not isinstance(kind, str) or kind not in PLAN_KINDS:
-                raise ValueError(f"{at}: kind must be one of 'l1', 'mse', 'mean', 'rel' (got {kind!r})")
-            if kind == "rel":
-                x, y, cc, sc = _check_rel(at, a, b, c, scale)
-                spec.append((_REL, sc, 0.0, False, False, 1, 0, cc))
-                tensors += [x.contiguous(), y.contiguous()]
-            else:
-                T = _check_term(at, "l1" if kind == "mean" else kind, a, b, c, scale)
-                spec.append((PLAN_KINDS[kind], T.scale, T.t_scalar, T.t is not None, T.w is not None, T.plane, T.cpl, 0.0))
-                tensors += [v.contiguous() for v in (T.x, T.t, T.w) if v is not None]       # (a no-op for a contiguous tensor)
-        dev = ops._current_device()
-        for v in tensors:
-            if v.device.index != dev:
-                raise RuntimeError(f"{where}: a tensor lives on {v.device} but the current device is cuda:{dev}; call "
-                                   "torch.cuda.set_device / use torch.cuda.device(...)")
-        return _PlanFn.apply(self, tuple(spec), *tensors)
+        spec, tensors = _checked_terms("dvc_amd.losses.Plan", terms,
+                                       "(kind, input, target, weights_or_None, scale) or (\"rel\", x, y, c, scale)", _plan_row)
+        return _PlanFn.apply(self, spec, *tensors)
 
 
 def relativistic_loss(x, y, c):

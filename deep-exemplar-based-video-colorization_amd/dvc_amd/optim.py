@@ -7,10 +7,9 @@ per parameter), and a `state_dict()` that `torch.optim.Adam` loads and vice vers
 decoupled_weight_decay, foreach=True, fused=True, tensor hyper-parameters, CPU / non-fp32 / sparse / non-contiguous tensors.
 
 Per step the host evaluates each tensor's scalars in double (per TENSOR: torch keeps `step` per parameter, and groups differ in
-`lr`), writes the tensor and chunk tables into a pinned staging buffer, sends them with one host-to-device copy on the current
-stream and launches once.  Two staging buffers alternate, each behind an event recorded after its copy, so a step never
-overwrites a buffer whose copy has not run yet.  The scalars change every step, so a step cannot be replayed from a captured
-graph: `step()` raises while the current stream is capturing.
+`lr`), packs the tensor and chunk tables into a pinned staging buffer, sends them with one host-to-device copy on the current
+stream and launches once; the staging discipline (and the resident tables' below) is dvc_amd.tables', described there once.
+The scalars change every step, so a step cannot be replayed from a captured graph: `step()` raises while the stream is capturing.
 
 `CapturableAdam` (below) is the variant that can: torch's `capturable=True` contract.  Its `step` tensors live on the device, a
 second small launch (dvc_adam_advance) advances them and rewrites the two step-dependent columns of the tensor table there, and the
@@ -27,7 +26,7 @@ import numpy as np
 import torch
 from torch.optim.optimizer import Optimizer
 
-from . import _lib, ops
+from . import _lib, ops, tables
 
 CHUNK = 4096  # elements per chunk == DVC_ADAM_CHUNK of include/dvc_hip.h (tests/test_adam_host.py holds the two together)
 TENSOR_DTYPE = np.dtype(_lib.DvcAdamTensor)
@@ -35,6 +34,7 @@ CHUNK_DTYPE = np.dtype(_lib.DvcAdamChunk)
 ADVANCE_DTYPE = np.dtype(_lib.DvcAdamAdvance)      # (CapturableAdam's third table)
 GUARD_DTYPE = np.dtype(_lib.DvcGradGuard)          # (GuardedAdam's device record)
 _REFUSED_FLAGS = ("maximize", "capturable", "differentiable", "decoupled_weight_decay")
+_Staging = tables.Staging       # (the name dvc_amd.losses and the tests know it by)
 
 
 def adam_scalars(step, lr, beta1, beta2, eps, weight_decay):
@@ -43,6 +43,11 @@ def adam_scalars(step, lr, beta1, beta2, eps, weight_decay):
     bc1 = 1.0 - beta1 ** step
     bc2 = 1.0 - beta2 ** step
     return (lr / bc1, 1.0 / math.sqrt(bc2), beta2, 1.0 - beta1, 1.0 - beta2, eps, weight_decay, 0.0)
+
+
+def n_chunks(counts):
+    """The number of records of chunk_table(counts), without building it."""
+    return sum((n + CHUNK - 1) // CHUNK for n in counts)
 
 
 def chunk_table(counts):
@@ -73,14 +78,32 @@ def vector_path(*addresses):
     return all(a % 16 == 0 for a in addresses)
 
 
-class _Staging:
-    """Two pinned buffers used in turn; `event[i]` is recorded after the copy out of buffer i."""
+def _capturing():
+    return torch.cuda.is_initialized() and torch.cuda.is_current_stream_capturing()
 
-    def __init__(self):
-        self.buf = [None, None]
-        self.event = [None, None]
-        self.counts = [None, None]      # the counts whose chunk table buffer i holds (at the offset they imply)
-        self.slot = 0
+
+def _refuse_capture(where, whose="tensors", advice=""):
+    """For calls whose tables are launch-time data: raise while the stream is capturing, before anything is allocated or launched."""
+    if _capturing():
+        raise RuntimeError(f"{where} cannot be captured into a graph: its tables carry the {whose}' addresses and are launch-time "
+                           f"data; call it outside the capture{advice}")
+
+
+def _send(st, records, counts, device):
+    """[records | chunk_table(counts)] through `st`'s next buffer into a table tensor that lives for one call (freed on return,
+    the allocator reuses it in stream order).  The chunk table is built only if the buffer does not already hold the one of
+    `counts`.  -> (table, the pinned buffer it was sent from, number of chunks)"""
+    n_c = n_chunks(counts)
+    c_bytes = n_c * CHUNK_DTYPE.itemsize
+    slot = st.acquire(records.nbytes + c_bytes)
+    if st.counts[slot] == counts:
+        tables.pack(st.buf[slot].numpy(), [records], tail_bytes=c_bytes)
+    else:
+        tables.pack(st.buf[slot].numpy(), [records, chunk_table(counts)])
+        st.counts[slot] = counts
+    table = tables.upload(st.buf[slot], records.nbytes + c_bytes, device)
+    st.sent(slot)
+    return table, st.buf[slot], n_c
 
 
 class Adam(Optimizer):
@@ -201,7 +224,7 @@ class Adam(Optimizer):
 
     @torch.no_grad()
     def step(self, closure=None):
-        if torch.cuda.is_initialized() and torch.cuda.is_current_stream_capturing():       # before anything is allocated or launched
+        if _capturing():        # before anything is allocated or launched
             raise RuntimeError("dvc_amd.optim.Adam: step() cannot be captured into a graph: its scalars (the bias corrections of "
                                "step t) change every step and are launch-time table entries; step outside the capture, or use "
                                "dvc_amd.optim.CapturableAdam")
@@ -235,32 +258,14 @@ class Adam(Optimizer):
             torch.autograd.graph.increment_version([p for p, _ in updated])
         return loss
 
-    def _launch(self, entries, device):
+    def _staging(self):
         st = self.__dict__.get("_dvc_staging")
-        if st is None:
-            st = self.__dict__["_dvc_staging"] = _Staging()
-        counts = tuple(e[5] for e in entries)
-        n_t = len(entries)
-        n_c = sum((n + CHUNK - 1) // CHUNK for n in counts)
-        t_bytes, c_bytes = n_t * TENSOR_DTYPE.itemsize, n_c * CHUNK_DTYPE.itemsize       # (80 n_t: the chunk table stays 16-byte aligned)
-        nbytes = t_bytes + c_bytes
-        slot = st.slot = 1 - st.slot
-        if st.event[slot] is not None:
-            st.event[slot].synchronize()        # the copy that last read this buffer (two steps ago) has run
-        if st.buf[slot] is None or st.buf[slot].numel() < nbytes:
-            st.buf[slot] = torch.empty(nbytes + nbytes // 4, dtype=torch.uint8, pin_memory=True)
-            st.counts[slot] = None
-        host = st.buf[slot].numpy()
-        host[:t_bytes].view(TENSOR_DTYPE)[:] = np.array([e[:6] + e[6] for e in entries], dtype=TENSOR_DTYPE)
-        if st.counts[slot] != counts:
-            host[t_bytes:nbytes].view(CHUNK_DTYPE)[:] = chunk_table(counts)
-            st.counts[slot] = counts
-        table = torch.empty(nbytes, dtype=torch.uint8, device=device)       # (freed on return: the allocator reuses it in stream order)
-        table.copy_(st.buf[slot][:nbytes], non_blocking=True)
-        if st.event[slot] is None:
-            st.event[slot] = torch.cuda.Event()
-        st.event[slot].record()
-        ops.adam_step(table, n_t, table[t_bytes:], n_c)
+        return st if st is not None else self.__dict__.setdefault("_dvc_staging", _Staging())
+
+    def _launch(self, entries, device):
+        tensors = np.array([e[:6] + e[6] for e in entries], dtype=TENSOR_DTYPE)
+        table, _, n_c = _send(self._staging(), tensors, tuple(e[5] for e in entries), device)
+        ops.adam_step(table, len(entries), table[tensors.nbytes:], n_c)
 
 
 # ---- the capturable variant: step counts and bias terms kept on the device
@@ -302,19 +307,15 @@ def build_capturable_tables(work):
     return tensors, chunk_table([w[1].numel() for w in work]), advance
 
 
-class _Resident:
-    """One table tensor on the device ([tensor records | chunk records | advance records]) and what it was built from."""
+class _Resident(tables.Resident):
+    """One table tensor on the device ([tensor records | chunk records | advance records | scratch]) and what it was built from."""
 
-    def __init__(self, key, table, n_t, n_c, params, pinned, stream):
-        t_bytes, c_bytes = n_t * TENSOR_DTYPE.itemsize, n_c * CHUNK_DTYPE.itemsize       # (80 n_t + 16 n_c: every table 8-byte aligned)
-        self.key, self.table, self.n_t, self.n_c, self.params = key, table, n_t, n_c, params
-        a_end = t_bytes + c_bytes + n_t * ADVANCE_DTYPE.itemsize
-        self.chunks, self.advance = table[t_bytes:t_bytes + c_bytes], table[t_bytes + c_bytes:a_end]
-        self.scratch = table[a_end:]        # (CapturableAdam._scratch_bytes: empty unless a subclass asks for some)
+    def __init__(self, key, table, c_at, a_at, end, n_t, n_c, params, pinned, stream):
+        super().__init__(key, table, pinned, stream)
+        self.n_t, self.n_c, self.params = n_t, n_c, params
+        self.chunks, self.advance = table[c_at:a_at], table[a_at:end]
+        self.scratch = table[end:]          # (CapturableAdam._scratch_bytes: empty unless a subclass asks for some)
         self.guard = None                   # (GuardedAdam: the record its launches on these tables write, kept alive with them)
-        self.pinned = pinned        # the buffer a CAPTURED upload reads on every replay (None for an eager upload)
-        self.stream = stream        # the last stream it was used on
-        self.captured = False
 
 
 class CapturableAdam(Adam):
@@ -329,15 +330,14 @@ class CapturableAdam(Adam):
     step advances nothing), fingerprints the addresses, element counts and hyper-parameters (`fingerprint`), and if nothing moved
     since the tables were uploaded it is exactly two launches: no copy, no allocation, no host arithmetic.  If something moved
     (a reallocated `.grad`, a gradient that went to None, a scheduler's new float `lr`, a loaded state) the tables are rebuilt and
-    uploaded from a pinned buffer under `_Staging`'s discipline.
+    uploaded from a pinned buffer under `tables.Staging`'s discipline.
 
     `step()` works under `torch.cuda.graph`.  Take one eager step (or load a state_dict) first: state created during a capture
-    would be zeroed again by every replay, so a captured step refuses to create it.  Tables uploaded during a capture are sent
-    from a pinned buffer of their own that is never rewritten, so the replay's copy node re-sends the same bytes, and the advance
-    launch that follows rewrites the two step-dependent columns from the device `step`: a replay is correct whatever the copy
-    restored.  Tables a graph refers to stay alive as long as the optimiser.  A float `lr` changed by a scheduler is seen by the
-    next eager `step()` but not by a replay (it is baked into the captured tables); a tensor `lr` updated in place is seen by
-    both.
+    would be zeroed again by every replay, so a captured step refuses to create it.  Tables uploaded during a capture, and tables
+    a graph refers to, are kept as dvc_amd.tables says; the replayed copy re-sends the same bytes and the advance launch that
+    follows rewrites the two step-dependent columns from the device `step`: a replay is correct whatever the copy restored.
+    A float `lr` changed by a scheduler is seen by the next eager `step()` but not by a replay (it is baked into the captured
+    tables); a tensor `lr` updated in place is seen by both.
 
     A replay runs no host code, so it cannot bump the parameters' version counters as the eager `step()` does: call
     `mark_updated()` after every replay.  Without it the modules' packed-weight caches, which are keyed on the version, go stale,
@@ -404,7 +404,7 @@ class CapturableAdam(Adam):
     # ---- pinned memory for an upload that is itself captured
     def _table_bytes_bound(self):
         params = [p for group in self.param_groups for p in group["params"]]
-        n_c = sum((p.numel() + CHUNK - 1) // CHUNK for p in params)
+        n_c = n_chunks(p.numel() for p in params)
         return len(params) * (TENSOR_DTYPE.itemsize + ADVANCE_DTYPE.itemsize) + n_c * CHUNK_DTYPE.itemsize
 
     def _ensure_spare(self):
@@ -427,7 +427,7 @@ class CapturableAdam(Adam):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        capturing = torch.cuda.is_initialized() and torch.cuda.is_current_stream_capturing()
+        capturing = _capturing()
         if capturing:
             for group in self.param_groups:
                 for p in group["params"]:
@@ -443,15 +443,7 @@ class CapturableAdam(Adam):
         res = self.__dict__.get("_dvc_resident")
         if res is None or res.key != key:
             res = self._upload(work, key, capturing)
-        stream = ops._stream_handle()
-        if capturing:
-            if not res.captured:        # a graph refers to these tables from now on: they live as long as the optimiser
-                res.captured = True
-                self.__dict__.setdefault("_dvc_captured", []).append(res)
-        elif stream != res.stream:
-            if not res.captured:        # (allocated on another stream: the allocator must not reuse it under this one's launches)
-                res.table.record_stream(torch.cuda.current_stream())
-            res.stream = stream
+        res.use(self.__dict__.setdefault("_dvc_captured", []) if capturing else None, capturing, ops._stream_handle())
         self._launch_resident(res, capturing)
         # the kernel wrote the parameters behind autograd's back: a graph that saved one must refuse its backward
         torch.autograd.graph.increment_version(res.params)
@@ -480,36 +472,22 @@ class CapturableAdam(Adam):
         """Rebuild the three tables and send them to a fresh table tensor with one host-to-device copy on the current stream."""
         tensors, chunks, advance = build_capturable_tables(work)
         n_t, n_c = len(tensors), len(chunks)
-        t_bytes, c_bytes, a_bytes = tensors.nbytes, chunks.nbytes, advance.nbytes
-        nbytes = t_bytes + c_bytes + a_bytes
-        st = None
+        nbytes = tensors.nbytes + chunks.nbytes + advance.nbytes
         if capturing:       # a buffer of its own, never rewritten: the replay's copy node reads it again
             pinned = self.__dict__.get("_dvc_spare")
             self.__dict__["_dvc_spare"] = None
             if pinned is None or pinned.numel() < nbytes:
                 pinned = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
         else:
-            st = self.__dict__.get("_dvc_staging")
-            if st is None:
-                st = self.__dict__["_dvc_staging"] = _Staging()
-            slot = st.slot = 1 - st.slot
-            if st.event[slot] is not None:
-                st.event[slot].synchronize()        # the copy that last read this buffer (two uploads ago) has run
-            if st.buf[slot] is None or st.buf[slot].numel() < nbytes:
-                st.buf[slot] = torch.empty(nbytes + nbytes // 4, dtype=torch.uint8, pin_memory=True)
+            st = self._staging()
+            slot = st.acquire(nbytes)
             pinned = st.buf[slot]
-        host = pinned.numpy()
-        host[:t_bytes].view(TENSOR_DTYPE)[:] = tensors
-        host[t_bytes:t_bytes + c_bytes].view(CHUNK_DTYPE)[:] = chunks
-        host[t_bytes + c_bytes:nbytes].view(ADVANCE_DTYPE)[:] = advance
-        table = torch.empty(nbytes + self._scratch_bytes(n_c), dtype=torch.uint8, device=work[0][1].device)
-        table[:nbytes].copy_(pinned[:nbytes], non_blocking=True)
-        if st is not None:
-            if st.event[slot] is None:
-                st.event[slot] = torch.cuda.Event()
-            st.event[slot].record()
-        res = _Resident(key, table, n_t, n_c, [w[1] for w in work], pinned if capturing else None, ops._stream_handle())
-        self.__dict__["_dvc_resident"] = res
+        (_, c_at, a_at), _ = tables.pack(pinned.numpy(), [tensors, chunks, advance])
+        table = tables.upload(pinned, nbytes, work[0][1].device, self._scratch_bytes(n_c))
+        if not capturing:
+            st.sent(slot)
+        res = self.__dict__["_dvc_resident"] = _Resident(key, table, c_at, a_at, nbytes, n_t, n_c, [w[1] for w in work],
+                                                         pinned if capturing else None, ops._stream_handle())
         return res
 
 
@@ -580,27 +558,17 @@ def _gradients(parameters, where, in_place):
 
 
 def _functional_norm(grads, max_norm, where):
-    """Upload the tables of `grads` under _Staging's discipline and launch dvc_grad_norm.  -> (table, n_t, chunks, n_c, guard)"""
-    if torch.cuda.is_initialized() and torch.cuda.is_current_stream_capturing():        # before anything is allocated or launched
-        raise RuntimeError(f"{where} cannot be captured into a graph: its tables carry the gradients' addresses and are launch-time "
-                           "data; call it outside the capture, or use dvc_amd.optim.GuardedAdam")
+    """Upload the tables of `grads` through _functional_staging and launch dvc_grad_norm.  -> (table, n_t, chunks, n_c, guard)"""
+    _refuse_capture(where, "gradients", ", or use dvc_amd.optim.GuardedAdam")
     tensors, chunks = build_norm_tables(grads)
     n_t, n_c = len(tensors), len(chunks)
     t_bytes, nbytes = tensors.nbytes, tensors.nbytes + chunks.nbytes
     st = _functional_staging
-    slot = st.slot = 1 - st.slot
-    if st.event[slot] is not None:
-        st.event[slot].synchronize()        # the copy that last read this buffer (two calls ago) has run
-    if st.buf[slot] is None or st.buf[slot].numel() < nbytes:
-        st.buf[slot] = torch.empty(nbytes + nbytes // 4, dtype=torch.uint8, pin_memory=True)
-    host = st.buf[slot].numpy()
-    host[:t_bytes].view(TENSOR_DTYPE)[:] = tensors
-    host[t_bytes:nbytes].view(CHUNK_DTYPE)[:] = chunks
+    slot = st.acquire(nbytes)
+    tables.pack(st.buf[slot].numpy(), [tensors, chunks])
     device = grads[0].device
-    table = torch.empty(nbytes + 8 * n_c, dtype=torch.uint8, device=device)     # (tables | partials; freed on return, in stream order)
-    table[:nbytes].copy_(st.buf[slot][:nbytes], non_blocking=True)
-    st.event[slot] = torch.cuda.Event()
-    st.event[slot].record()
+    table = tables.upload(st.buf[slot], nbytes, device, 8 * n_c)        # (tables | partials; freed on return, in stream order)
+    st.sent(slot)
     guard = new_guard(device)
     ops.grad_norm(table, n_t, table[t_bytes:nbytes], n_c, table[nbytes:].view(torch.float64), max_norm, guard)
     return table, n_t, table[t_bytes:nbytes], n_c, guard
